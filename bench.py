@@ -11,14 +11,20 @@ Multi-GPU (launched by torch.distributed.run): one process per GPU, utterance-sh
 (weak scaling: 1024 frames per GPU per step), per-layer RCCL all-reduce of the gradients over
 xGMI, global-bunch GRADDIVFRM normalisation.  torch is used only for the gloo rendezvous /
 barrier / max-reduce of the timings (tnet_amd maps torch's ROCm runtime before the library whenever
-torch is installed: one HIP runtime and one RCCL per process, whatever the import order).  After the
-timed region every rank checksums its parameters and the ranks compare them: replicas that differ
+torch is installed: one HIP runtime and one RCCL per process, whatever the import order).  With --full, after
+the timed region every rank checksums its parameters and the ranks compare them: replicas that differ
 (a broken exchange) end the run with a non-zero exit instead of a number; before that, one extra step verifies the
 reductions themselves (rccl_check: every layer's RCCL-reduced gradient against a float64 gloo sum of the ranks'
 local gradients, tnet_amd/dpcheck.py -- a wrong reduction hands every rank the same wrong sum, which the replica
 checksum cannot see; exit 4 on a mismatch).
 
-Extra JSON fields: roofline (dominant kernel = the 2048x2048 affine-layer GEMMs, timed with hipEvents
+A plain run (`bench.py --gpus 1 --steps N --warmup W`) does only what the headline figure needs: set-up, the
+prewarm and warm-up steps, the N timed steps, the result line.  --dump-outputs DIR also writes what the timed
+steps computed (dump_outputs, right after the timed region).  Everything else -- the roofline and per-kernel
+regions, the CPU baseline, the reduction and replica checks -- runs only with --full, each under its own
+option as before (--kernel-timing, --breakdown-steps, --no-cpu-baseline, --rccl-check-shard).
+
+Extra JSON fields with --full: roofline (dominant kernel = the 2048x2048 affine-layer GEMMs, timed with hipEvents
 on the library stream over K further steps of the same workload right after the timed region: one
 event pair per run of back-to-back roofline launches -- the 3 hidden forward GEMMs, and the 6 hidden
 backward + update GEMMs -- and none in the value region, since every event pair adds stream time),
@@ -103,6 +109,33 @@ def param_checksum(net):
             h.update(a.tobytes())
             tot += float(a.sum(dtype=np.float64))
     return h.hexdigest()[:16], repr(tot)
+
+
+DUMP_CAP = 1 << 21  # elements stored of one dumped array (8 MB of float32)
+
+
+def dump_outputs(outdir, net, obj):
+    """--dump-outputs: what the timed steps hand their caller after the last of them -- every affine layer's
+    weights and bias as that step's update left them (W<k>.npy, b<k>.npy, float32 as on the device) and the
+    objective's accumulators (objective.npy: error, frames, correct as float64).  An array of more than DUMP_CAP
+    elements is stored as a fixed sample: its elements at DUMP_CAP flat indices, ascending, drawn by a generator
+    seeded with the array's position in the dump -- the same indices in every run and every build (dnn4: 36 MB in
+    all, dnn5: 44 MB).  The inputs are seeded (build_network, synth_frames, the trainer's shuffle), so two runs
+    with the same arguments dump the outputs of the same computation."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = []
+    for k, (W, b) in enumerate(net.linear_params()):
+        arrays += [(f"W{k}", W), (f"b{k}", b)]
+    arrays.append(("objective", np.array(obj.stats(), np.float64)))
+    total = 0
+    for i, (name, a) in enumerate(arrays):
+        if a.size > DUMP_CAP:
+            idx = np.random.default_rng(5000 + i).integers(0, a.size, DUMP_CAP)
+            a = np.ascontiguousarray(a).ravel()[np.sort(idx)]
+        total += a.nbytes
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    if total > 64 << 20:
+        raise SystemExit(f"--dump-outputs wrote {total} bytes, more than 64 MB: lower DUMP_CAP for this network")
 
 
 def roofline_shape(dims):
@@ -302,6 +335,12 @@ def main():
     ap.add_argument("--bunch", type=int, default=1024)
     ap.add_argument("--cache", type=int, default=65536, help="frames resident per GPU")
     ap.add_argument("--lr", type=float, default=1.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything that is not the headline figure: the roofline and "
+                         "per-kernel regions, the CPU baseline, the reduction and replica checks (each under its own "
+                         "option below); without it none of them runs and the result line has only the figure's fields")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what they computed as DIR/<name>.npy (dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-threads", type=int, default=0)
     ap.add_argument("--comm", default="rccl", choices=["rccl", "host"],
@@ -399,12 +438,15 @@ def main():
     trainer.replay(args.steps)
     barrier()
     dt = time.perf_counter() - t0
+    # the outputs of the last timed step, before any --full region trains further
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, obj)
     # roofline region: the next K steps of the same workload with one hipEvent pair around each run of
     # back-to-back roofline kernels (each pair adds ~3 us of stream time, so not inside the value region)
     buf = ctypes.create_string_buffer(1 << 16)
     kern = {}
     roof_shape = roofline_shape(dims)
-    if args.kernel_timing:
+    if args.full and args.kernel_timing:
         # "gemm_*<shape>": the GEMM launches of the roofline shape only (not the data-parallel SGD applies of
         # that shape, which run on the apply stream); runs also close at every exchange step
         check(lib().tnet_kernel_timing_filter(("gemm_*" + roof_shape).encode()), "timing_filter")
@@ -415,7 +457,7 @@ def main():
         kern = parse_kernel_report(buf.value.decode())
     # per-kernel breakdown (every launch event-timed) in extra steps outside the timed region
     breakdown = {}
-    if args.breakdown_steps > 0:
+    if args.full and args.breakdown_steps > 0:
         check(lib().tnet_kernel_timing_filter(b""), "timing_filter")
         check(lib().tnet_kernel_timing(1), "kernel_timing")
         trainer.replay(args.breakdown_steps)
@@ -423,7 +465,7 @@ def main():
         check(lib().tnet_kernel_timing_report(buf, len(buf)), "kernel_timing_report")
         breakdown = parse_kernel_report(buf.value.decode())
     # the reduction check: one more step, after every measured region (synchronous copies)
-    rccl_check = reduction_checks(args, comm, trainer, dist, rank, world) if comm is not None else None
+    rccl_check = reduction_checks(args, comm, trainer, dist, rank, world) if args.full and comm is not None else None
     if rccl_check is not None and not rccl_check["ok"]:  # the TIMED mode's reductions are wrong: no number
         print("bench: the reduced gradients differ from the gloo float64 sum of the local gradients: " +
               json.dumps(rccl_check), file=sys.stderr)
@@ -437,8 +479,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
-    replicas = param_checksum(net)
-    if dist is not None:
+    replicas = param_checksum(net) if args.full else None
+    if args.full and dist is not None:
         got = [None] * world
         dist.all_gather_object(got, replicas)
         if any(g != got[0] for g in got):
@@ -482,7 +524,7 @@ def main():
                    "rate_unit": "TFLOP/s" if k.startswith("gemm") else "GB/s"} for k, v in sorted(breakdown.items())}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import cpu_baseline
         try:
             cpu = cpu_baseline.reference_cpu_baseline(dims, bunch=B, threads=args.cpu_threads or None)
@@ -516,17 +558,23 @@ def main():
                        "whole_step_frac_of_fp32_peak": round(value * flops_per_frame(dims) / 1e12 / world /
                                                              PEAK_FP32_MFMA, 4),
                        "gemm_share_of_kernel_time": round(all_gemm_ms / all_ms, 4) if all_ms else None},
-            "roofline": roof,
-            "cpu_baseline": cpu,
-            "replica_check": {"ranks": world, "identical": True, "param_sha256_16": replicas[0],
-                              "param_sum": replicas[1]},
-            "rccl_check": rccl_check,
             "runtime": mapped_runtime(),
-            "kernels": kernels,
-            "kernels_note": f"every launch event-timed, {args.breakdown_steps} extra steps after the timed region "
-                            "(event pairs add stream time: the value region has none, the roofline region times "
-                            "only the roofline kernels)",
+            "full": args.full,
         }
+        if args.dump_outputs:
+            line["outputs"] = args.dump_outputs
+        if args.full:
+            line.update({
+                "roofline": roof,
+                "cpu_baseline": cpu,
+                "replica_check": {"ranks": world, "identical": True, "param_sha256_16": replicas[0],
+                                  "param_sum": replicas[1]},
+                "rccl_check": rccl_check,
+                "kernels": kernels,
+                "kernels_note": f"every launch event-timed, {args.breakdown_steps} extra steps after the timed region "
+                                "(event pairs add stream time: the value region has none, the roofline region times "
+                                "only the roofline kernels)",
+            })
         os.write(result_fd, (json.dumps(line) + "\n").encode())
     # release the library objects in dependency order (trainer -> objective / network -> communicator)
     # while the HIP runtime and the process group are still up

@@ -8,6 +8,7 @@ inputs we generate here (seeded) and the outputs the reference computed on them.
 
   steps_tiny.npz       24:32:32:10 sigmoid MLP, bunch 16, 4 SGD steps (CPU TNet semantics)
   steps_slice.npz      598:128:135 MLP3-shaped slice, bunch 64, 3 SGD steps, weight decay on
+                       (+ steps_slice.part1.npz: tests/golden_io.py)
   shuffle.npz          cache permutations for (seed, n, cache, bunch) -- lrand48 + random_shuffle
   epoch_mlp3.json      one TNet epoch (THREADS=1) on a seeded synthetic 598-dim corpus with the
                        598:1024:135 MLP3: the reference's own Report() line and FPS
@@ -25,6 +26,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, os.path.join(REPO, "nnet-asr_amd"))
+sys.path.insert(0, os.path.join(REPO, "tests"))
+from golden_io import save_npz_parts  # noqa: E402
 from tnet_amd import formats  # noqa: E402
 
 REF = os.path.join(REPO, "oracle", "_ref")
@@ -72,7 +75,7 @@ def run_steps(name, dims, bunch, nsteps, lr, wc, seed, unlabeled=(), keep_all=Tr
             arrs["xent_sum"] = np.float64(err)
             arrs["frames"] = np.int64(frames)
             arrs["report"] = np.array(f.read().strip())
-    np.savez_compressed(os.path.join(HERE, name), **arrs)
+    save_npz_parts(os.path.join(HERE, name), arrs)  # (steps_slice: two parts, each under 1 MiB)
     print("wrote", name)
 
 

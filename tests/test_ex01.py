@@ -36,6 +36,7 @@ import numpy as np
 import pytest
 
 import oracle as orc
+from golden_io import load_npz
 from tnet_amd import formats, newbob
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -235,7 +236,7 @@ def test_first_steps_on_real_frames_match_reference():
     init_cfg, cfg = _epoch_cfg(mk.STEPS["epoch"])
     n = mk.STEPS["nsteps"]
     X, lab = mk.step_inputs(cfg, n)
-    g = np.load(os.path.join(GOLD, "ex01_steps.npz"))
+    g = load_npz(os.path.join(GOLD, "ex01_steps.npz"))
     net = tnet_amd.Network.from_layers(formats.round_trip_text(
         formats.gen_mlp_init(init_cfg["dims"], seed=init_cfg["seed"]), 6))
     net.set_learn_rate(cfg["lr"])

@@ -15,11 +15,12 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import oracle as orc  # noqa: E402
+from golden_io import load_npz  # noqa: E402
 from tnet_amd import DeviceArray, Network, Objective, Trainer, formats  # noqa: E402
 
 
 def _golden(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    return load_npz(os.path.join(golden_dir, name))
 
 
 def _net_from(g, prefix, dims):

@@ -6,10 +6,11 @@ import numpy as np
 import pytest
 
 import oracle as orc
+from golden_io import load_npz
 
 
 def _load(golden_dir, name):
-    return np.load(os.path.join(golden_dir, name), allow_pickle=False)
+    return load_npz(os.path.join(golden_dir, name))
 
 
 def _weights(g, prefix, nl):
@@ -61,7 +62,7 @@ def test_gpu_semantics_reduce_to_cpu(golden_dir):
 
 def test_shuffle_permutations(golden_dir):
     g = _load(golden_dir, "shuffle.npz")
-    for key in g.files:
+    for key in g:
         _, seed, n, cache, bunch = key.split("_")
         seed, n, cache, bunch = int(seed), int(n), int(cache), int(bunch)
         sched = orc.epoch_schedule([n], cache, bunch, seed).reshape(-1)

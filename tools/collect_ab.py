@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Collect bench.py A/B runs (one JSON line per file) into one evidence file: per arm the values, steps, roofline
-fractions and the per-kernel event-timed averages of every run.
+fractions and the per-kernel event-timed averages of every run (the last two from `bench.py --full` runs only).
 
 usage: python tools/collect_ab.py OUT.json "what was compared" ARM=glob [ARM=glob ...]"""
 import glob

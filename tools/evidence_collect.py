@@ -1,9 +1,9 @@
-"""Turn one tools/evidence_configs.sh run (gpurun_out/cfg) into the round's committed evidence:
+"""Turn one tools/evidence_configs.sh run (its output directory) into the round's committed evidence:
 
-usage: python tools/evidence_collect.py gpurun_out/cfg rNN
+usage: python tools/evidence_collect.py OUTDIR rNN
 
-  profiles/<rNN>_bench_mlp3.json              bench.py --config mlp3 line (BASELINE config 2)
-  profiles/<rNN>_bench_dnn5.json              bench.py --config dnn5 line (BASELINE config 3 network)
+  profiles/<rNN>_bench_mlp3.json              bench.py --full --config mlp3 line (BASELINE config 2)
+  profiles/<rNN>_bench_dnn5.json              bench.py --full --config dnn5 line (BASELINE config 3 network)
   profiles/<rNN>_configs_4_5.json             tools/rbm_bench.py (config 4) + tools/rnn_bench.py (config 5)
   profiles/<rNN>_mlp3_kernel_trace_stats.txt  rocprofv3 --kernel-trace --stats summary of the MLP3 step
   profiles/<rNN>_rbm256_kernel_stats.txt      the same for the bunch-256 RBM step
@@ -45,8 +45,8 @@ def main():
         json.dump(conf, f, indent=1)
     with open(os.path.join(prof, f"{tag}_mlp3_kernel_trace_stats.txt"), "w") as f:
         f.write(stats_txt(os.path.join(src, "prof_mlp3", "mlp3_kernel_stats.csv"),
-                          "rocprofv3 --kernel-trace --stats -- python3 bench.py --config mlp3 --no-cpu-baseline "
-                          "--steps 300 --kernel-timing 0 (config 2, 598:1024:135, bunch 1024)"))
+                          "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --config mlp3 "
+                          "--no-cpu-baseline --steps 300 --kernel-timing 0 (config 2, 598:1024:135, bunch 1024)"))
     with open(os.path.join(prof, f"{tag}_rbm256_kernel_stats.txt"), "w") as f:
         f.write(stats_txt(os.path.join(src, "prof_rbm256", "rbm_kernel_stats.csv"),
                           "rocprofv3 --kernel-trace --stats -- python3 tools/rbm_bench.py 256 500 1 (config 4, "

@@ -1,6 +1,6 @@
 """Turn one tools/profile_round.sh run into the round's committed evidence under profiles/.
 
-usage: python tools/roofline_evidence.py gpurun_out rNN
+usage: python tools/roofline_evidence.py OUTDIR rNN      (OUTDIR: the directory profile_round.sh wrote)
 
   profiles/<rNN>_bench_dnn4.json              the bench line of that run
   profiles/<rNN>_bench_dnn4_kernel_stats.csv  rocprofv3 --kernel-trace --stats summary (same command)
@@ -94,7 +94,7 @@ def main():
     cls = classify_trace(os.path.join(src, "prof_stats", "bench_kernel_trace.csv"))
     allv = cls["fwd"] + cls["bwd"] + cls["upd"] + cls["pair"]
     prof_bench = json.loads(open(os.path.join(src, "bench_prof.json")).read().strip().splitlines()[-1])
-    tr = {"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --no-cpu-baseline",
+    tr = {"source": "rocprofv3 --kernel-trace --stats -- python3 bench.py --full --no-cpu-baseline",
           "per_class_avg_us": {k: round(sum(v) / len(v), 2) for k, v in cls.items() if v},
           "per_class_launches": {k: len(v) for k, v in cls.items()},
           "roofline_set_avg_us_rocprof": round(sum(allv) / len(allv), 2),
