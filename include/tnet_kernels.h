@@ -456,7 +456,15 @@ int tnet_argmax_correct(const unsigned long long* keys, const int* labels, int T
  *                              d_i) -- b' the bias after the pending update (bnext / cbnext written, the
  *                              tnet_rnn_update chain) -- and that update of W (rows x H, tnet_rnn_update's
  *                              per-element arithmetic with history head / R and d_i = D rows) in extra workgroups
- * The recurrent output differs from the materialised product by fp32 reassociation only (test_gpu_rnn.py). */
+ * The recurrent output differs from the materialised product (tnet_rnn_update -> tnet_gemv_rowvec_partial ->
+ * tnet_rnn_out_full) by fp32 reassociation only; everything else -- the output-layer side, the look-ahead partials,
+ * the history push, the bias copy, the update of W and of the bias -- is bit-identical to the entry points named
+ * (tests/test_gpu_rnn_ahead.py at kernel level, up to H = 2048 and N = 4096; the trainer against the oracle in
+ * tests/test_gpu_rnn.py).  TNET_RNN_AHEAD=0 is the strict-parity mode: the older chain (the update folded into the
+ * next frame's tnet_gemv_rowvec_partial_update, or on its own past 9 steps), per element the component chain's
+ * arithmetic; it is also what bptt + 1 > 9 or H % 4 != 0 take (test_rnn_strict_parity_mode runs both modes).
+ * TNET_ERR_UNSUPPORTED, nothing launched: N > 4096 (pairs > 64), steps > 9, steps >= R, and for
+ * tnet_rnn_out_full_ahead H > 2048, H % 4 != 0, ldw or ldd no multiple of 4, hslices != ceil(rows / 64). */
 int tnet_rnn_out_full_ahead(const float* hpart, int hslices, const float* hb, float* h, int H, const float* Wo,
                             int ldwo, int N, const float* bo, float* z, double* smx, const float* dpart, const float* D,
                             int ldd, int steps, float lr, float mmt, float wc, const float* cb, float* bnext,

@@ -24,7 +24,8 @@ def S():
     return lib().tnet_stream()
 
 
-@pytest.mark.parametrize("K,N,act", [(1, 1, 0), (952, 512, 1), (440, 135, 0), (2100, 70, 1)])
+@pytest.mark.parametrize("K,N,act", [(1, 1, 0), (952, 512, 1), (440, 135, 0), (2100, 70, 1), (1036, 1028, 1),
+                                     (2088, 2048, 1)])
 def test_gemv_rowvec(K, N, act):
     rng = np.random.default_rng(K + N)
     v = rng.standard_normal(K).astype(np.float32)
@@ -40,7 +41,8 @@ def test_gemv_rowvec(K, N, act):
 
 
 @pytest.mark.parametrize("r0,nrows,n,beta,sig", [(0, 440, 512, 0.0, False), (440, 512, 512, 1.0, True),
-                                                  (3, 7, 13, 0.5, True)])
+                                                  (3, 7, 13, 0.5, True), (8, 1028, 1028, 0.0, True),
+                                                  (40, 2048, 2048, 0.0, True)])
 def test_gemv_rows(r0, nrows, n, beta, sig):
     rng = np.random.default_rng(nrows)
     W = rng.standard_normal((r0 + nrows, n)).astype(np.float32)
@@ -68,13 +70,32 @@ def test_recurrent_text_round_trip(tmp_path):
     np.testing.assert_allclose(back[0].W, layers[0].W, rtol=1e-5, atol=1e-7)
 
 
-@pytest.mark.parametrize("bptt,mmt,wc", [(4, 0.0, 0.0), (2, 0.5, 1e-4), (0, 0.0, 0.0)])
-def test_rnn_trainer_matches_oracle(bptt, mmt, wc):
-    """Two utterances through TRecurrentCu semantics (history reset per utterance), the per-frame launch chain."""
-    nIn, H, Sd, lr = 24, 32, 10, 0.05
+_SHORT = (1, 2, 1, 7, 3)  # utterances of 1 and 2 frames, a 1-frame utterance between longer ones
+
+
+@pytest.mark.parametrize("bptt,mmt,wc,nIn,H,lens", [
+    pytest.param(4, 0.0, 0.0, 24, 32, (60, 45), id="4-0.0-0.0"),
+    pytest.param(2, 0.5, 1e-4, 24, 32, (60, 45), id="2-0.5-0.0001"),
+    pytest.param(0, 0.0, 0.0, 24, 32, (60, 45), id="0-0.0-0.0"),
+    pytest.param(8, 0.5, 1e-4, 24, 32, (60, 45), id="bptt8-last-look-ahead-depth"),
+    pytest.param(9, 0.5, 1e-4, 24, 32, (60, 45), id="bptt9-update-on-its-own"),
+    pytest.param(12, 0.0, 0.0, 24, 32, (60, 45), id="bptt12"),
+    pytest.param(4, 0.5, 1e-4, 24, 30, (60, 45), id="H30-folded-update"),
+    pytest.param(2, 0.5, 1e-4, 8, 516, (12, 9, 5), id="H516-look-ahead"),
+    pytest.param(4, 0.5, 1e-4, 24, 32, _SHORT, id="short-utterances"),
+    pytest.param(9, 0.0, 0.0, 24, 32, _SHORT, id="short-utterances-bptt9"),
+    pytest.param(2, 0.5, 1e-4, 24, 30, _SHORT, id="short-utterances-H30"),
+])
+def test_rnn_trainer_matches_oracle(bptt, mmt, wc, nIn, H, lens):
+    """Utterances through TRecurrentCu semantics (history reset per utterance), the per-frame launch chain: the
+    look-ahead chain (bptt + 1 <= 9 steps and H % 4 = 0, up to its last depth bptt = 8 and at H > 512), the older
+    chain with the update folded into the next forward (H % 4 != 0), and with the update on its own (bptt + 1 > 9
+    steps: the folded kernel refuses, CuRecurrent::RunUpdate); utterances of 1 and 2 frames exercise the look-ahead
+    state (no look-ahead from an utterance's last frame, its update never deferred: no state leaves the utterance)."""
+    Sd, lr = 10, 0.05
     rng = np.random.default_rng(bptt)
     layers = formats.round_trip_text(formats.gen_recurrent_init(nIn, H, Sd, seed=7), 9)
-    feats = [rng.standard_normal((T, nIn)).astype(np.float32) for T in (60, 45)]
+    feats = [rng.standard_normal((T, nIn)).astype(np.float32) for T in lens]
     labels = [rng.integers(0, Sd, len(f)).astype(np.int32) for f in feats]
     net = Network.from_layers(layers)
     net.set_learn_rate(lr)
@@ -112,21 +133,31 @@ def _train_rnn(layers, feats, labels, bptt, lr, mmt, wc, generic, crossval=False
         os.environ.pop("TNET_RNN_GENERIC", None)
 
 
-@pytest.mark.parametrize("S,bptt,mmt,wc", [(10, 4, 0.0, 0.0), (135, 2, 0.5, 1e-4), (4000, 4, 0.9, 0.0),
-                                           (37, 0, 0.0, 1e-3), (135, 8, 0.0, 0.0)])
-def test_rnn_fused_frame_matches_component_chain(S, bptt, mmt, wc):
+@pytest.mark.parametrize("S,bptt,mmt,wc,H,lens", [
+    pytest.param(10, 4, 0.0, 0.0, 64, (50, 33), id="10-4-0.0-0.0"),
+    pytest.param(135, 2, 0.5, 1e-4, 64, (50, 33), id="135-2-0.5-0.0001"),
+    pytest.param(4000, 4, 0.9, 0.0, 64, (50, 33), id="4000-4-0.9-0.0"),
+    pytest.param(37, 0, 0.0, 1e-3, 64, (50, 33), id="37-0-0.0-0.001"),
+    pytest.param(135, 8, 0.0, 0.0, 64, (50, 33), id="135-8-0.0-0.0"),
+    pytest.param(135, 9, 0.5, 1e-4, 64, (50, 33), id="bptt9-update-on-its-own"),
+    pytest.param(135, 4, 0.5, 1e-4, 66, (50, 33), id="H66-folded-update"),
+    pytest.param(135, 4, 0.5, 1e-4, 64, _SHORT, id="short-utterances"),
+    pytest.param(135, 9, 0.5, 1e-4, 66, _SHORT, id="short-utterances-older-chain"),
+])
+def test_rnn_fused_frame_matches_component_chain(S, bptt, mmt, wc, H, lens):
     """the fused per-frame launch chain vs the component-by-component chain (Propagate, EvaluateLabels,
-    Backpropagate + Update per layer) on the same utterances"""
-    nIn, H, lr = 40, 64, 0.02
+    Backpropagate + Update per layer) on the same utterances; bptt = 9 and H = 66 take the older fused chain
+    (the update on its own / folded into the next forward), the short utterances the look-ahead state's edges"""
+    nIn, lr = 40, 0.02
     rng = np.random.default_rng(S)
     layers = formats.gen_recurrent_init(nIn, H, S, seed=11)
-    feats = [rng.standard_normal((T, nIn)).astype(np.float32) for T in (50, 33)]
+    feats = [rng.standard_normal((T, nIn)).astype(np.float32) for T in lens]
     labels = [rng.integers(0, S, len(f)).astype(np.int32) for f in feats]
     labels[1][::9] = -1  # unlabeled frames: zero target
     a = _train_rnn(layers, feats, labels, bptt, lr, mmt, wc, generic=False)
     b = _train_rnn(layers, feats, labels, bptt, lr, mmt, wc, generic=True)
     (ea, fa, ca), (eb, fb, cb) = a[0], b[0]
-    assert fa == fb == 83
+    assert fa == fb == sum(lens)
     np.testing.assert_allclose(ea, eb, rtol=1e-5)
     assert abs(ca - cb) <= 1
     for x, y in zip(a[1] + a[2], b[1] + b[2]):
@@ -134,12 +165,13 @@ def test_rnn_fused_frame_matches_component_chain(S, bptt, mmt, wc):
 
 
 @pytest.mark.parametrize("crossval", [False, True])
-@pytest.mark.parametrize("S,bptt,mmt", [(135, 4, 0.0), (4000, 2, 0.5)])
+@pytest.mark.parametrize("S,bptt,mmt", [(135, 4, 0.0), (4000, 2, 0.5), (135, 9, 0.5)])
 def test_rnn_graph_replay_matches_eager(S, bptt, mmt, crossval):
     """the per-frame chain recorded once per utterance length and replayed as a hipGraph (default)
     vs the same chain launched eagerly (TNET_RNN_GRAPH=0): bit-identical statistics and weights.
     Lengths repeat (recorded on the second sighting, replayed from the third), interleave, and the
-    learning rate changes between passes (a new key: recorded again)."""
+    learning rate changes between passes (a new key: recorded again).  bptt = 9: the older chain (10 steps: the
+    update on its own) recorded and replayed."""
     nIn, H = 40, 64
     rng = np.random.default_rng(S + bptt)
     layers = formats.gen_recurrent_init(nIn, H, S, seed=13)
@@ -261,7 +293,9 @@ def test_affine_bwd_update_row(mmt, n_in, n_out):
         np.testing.assert_array_equal(dC.numpy(), corr)
 
 
-@pytest.mark.parametrize("nIn,H,N,t", [(440, 512, 4000, 17), (440, 512, 135, 3), (30, 70, 300, -1), (8, 64, 5, 9)])
+@pytest.mark.parametrize("nIn,H,N,t", [(440, 512, 4000, 17), (440, 512, 135, 3), (30, 70, 300, -1), (8, 64, 5, 9),
+                                       (40, 516, 1025, 1024), (8, 1028, 135, 134), (600, 512, 135, 0),
+                                       (40, 2048, 4096, 4095)])
 def test_rnn_output_chain_kernels(nIn, H, N, t):
     """tnet_gemv_rowvec_partial -> tnet_rnn_out_partial -> tnet_rnn_out_stats -> tnet_rnn_out_bwd_update
     (the fused frame's output side) vs numpy in fp64: h, z, the softmax error inside the SGD of Wo / bo,
@@ -320,7 +354,9 @@ def test_rnn_output_chain_kernels(nIn, H, N, t):
     assert st2.numpy()[0][1] == float(int(np.argmax(y.numpy().ravel())) == (tt if tt >= 0 else 0))
 
 
-@pytest.mark.parametrize("nIn,H,N,t", [(440, 512, 4000, 17), (440, 512, 135, 3), (30, 70, 300, -1), (8, 64, 5, 9)])
+@pytest.mark.parametrize("nIn,H,N,t", [(440, 512, 4000, 17), (440, 512, 135, 3), (30, 70, 300, -1), (8, 64, 5, 9),
+                                       (40, 516, 1025, 1024), (8, 1028, 135, 134), (600, 512, 135, 0),
+                                       (40, 2048, 4096, 4095)])
 def test_rnn_out_full(nIn, H, N, t):
     """tnet_rnn_out_full (the trainer's output side: h finished by every workgroup, complete z per 64
     columns, one softmax pair per 64 columns) -> tnet_rnn_out_bwd_update with ceil(N/64) pairs vs numpy
@@ -416,3 +452,61 @@ def test_gemv_rowvec_partial_update(nIn, H, steps, R, head, mmt, wc):
     assert lib().tnet_gemv_rowvec_partial_update(dummy.ptr, 8, dummy.ptr, 8, None, dummy.ptr, 64, 8, dummy.ptr,
                                                  dummy.ptr, 64, 0, 4, dummy.ptr, 64, 4, dummy.ptr, dummy.ptr, lr,
                                                  mmt, wc, S()) != 0
+
+
+def test_rnn_strict_parity_mode(tmp_path):
+    """TNET_RNN_AHEAD is read once per process, so each mode trains in a process of its own (tests/rnn_modes_worker.py,
+    one after the other): 135 and 4000 outputs x bptt 0 and 4 with momentum and weight cost, fused chain and component
+    chain, plus one 300-frame utterance on the fused chain.
+      TNET_RNN_AHEAD=0 (the strict-parity mode: the older fused chain): fused vs component chain at
+        test_rnn_fused_frame_matches_component_chain's rtol 1e-4 / atol 1e-6 (xent rtol 1e-5);
+      both modes vs the oracle (orc.RNN) at test_rnn_trainer_matches_oracle's tolerances, the 300-frame utterance too.
+    The largest parameter difference between the two modes after the 300-frame utterance is printed: the look-ahead
+    chain's drift from the strict chain.  Observed on MI355X: 5.96e-8 absolute (one ulp of a weight in
+    [0.25, 0.5); 1.56e-7 of the largest parameter) -- not zero, so the two processes did run different chains; a
+    record, not a threshold."""
+    import subprocess
+    import sys
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    got = {}
+    for mode in ("0", "default"):
+        env = dict(os.environ)
+        env.pop("TNET_RNN_AHEAD", None)
+        if mode == "0":
+            env["TNET_RNN_AHEAD"] = "0"
+        out = str(tmp_path / f"rnn_{mode}.npz")
+        p = subprocess.run([sys.executable, os.path.join(repo, "tests", "rnn_modes_worker.py"), out],
+                           capture_output=True, text=True, timeout=300, env=env)
+        assert p.returncode == 0, p.stderr[-3000:]
+        got[mode] = dict(np.load(out))
+    names = sorted({k.split("/")[0] for k in got["0"]})
+    assert names == ["long", "s135_b0", "s135_b4", "s4000_b0", "s4000_b4"]
+    params = ("Wr", "br", "W2", "b2")
+    for name in names:
+        g0, g1 = ({k[len(name) + 1:]: v for k, v in got[m].items() if k.startswith(name + "/")} for m in ("0", "default"))
+        for k in g0:
+            if k.startswith("in/"):
+                np.testing.assert_array_equal(g0[k], g1[k], err_msg=k)  # the same corpus in both processes
+        if name != "long":
+            (ea, fa, ca), (eb, fb, cb) = g0["fused/stats"], g0["generic/stats"]
+            assert fa == fb == 83
+            np.testing.assert_allclose(ea, eb, rtol=1e-5, err_msg=name)
+            assert abs(ca - cb) <= 1
+            for k in params:
+                np.testing.assert_allclose(g0["fused/" + k], g0["generic/" + k], rtol=1e-4, atol=1e-6,
+                                           err_msg=f"{name} {k}: TNET_RNN_AHEAD=0 fused vs component chain")
+        m = orc.RNN(g0["in/Wr"], g0["in/br"], g0["in/W2"], g0["in/b2"])
+        u = 0
+        while f"in/feat{u}" in g0:
+            m.utterance(g0[f"in/feat{u}"], g0[f"in/lab{u}"], int(g0["in/bptt"]), 0.02, 0.5, 1e-4)
+            u += 1
+        for mode, g in (("TNET_RNN_AHEAD=0", g0), ("default", g1)):
+            err, frames, correct = g["fused/stats"]
+            assert frames == m.frames
+            np.testing.assert_allclose(err, m.xent, rtol=1e-4, err_msg=f"{name} {mode}")
+            assert abs(correct - m.correct) <= 1
+            for k, ref in zip(params, (m.Wr, m.br, m.W2, m.b2)):
+                np.testing.assert_allclose(g["fused/" + k], ref, rtol=2e-3, atol=2e-5, err_msg=f"{name} {mode} {k}")
+    drift = max(float(np.abs(got["0"][f"long/fused/{k}"] - got["default"][f"long/fused/{k}"]).max()) for k in params)
+    scale = max(float(np.abs(got["0"][f"long/fused/{k}"]).max()) for k in params)
+    print(f"rnn look-ahead drift after 300 frames: max |dp| = {drift:.3g} ({drift / scale:.3g} of max |p|)")
