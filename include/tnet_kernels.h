@@ -507,6 +507,32 @@ int tnet_rnn_update(float* W, int ldw, int rows, int nout, const float* hist, in
                     const float* D, int ldd, int steps, float* b, float* corr_b, float lr, float mmt, float wc,
                     void* stream);
 
+/* ---- <sharedlinearity> (CuSharedLinearity, cuSharedLinearity.cc:10-96): one W [in x out] on the n_inst
+ * column windows X_i = X[:, i*in : (i+1)*in] of X [rows x n_inst*in]; Y and E are [rows x n_inst*out].  Each
+ * entry point replaces the reference's n_inst OffsetGemm calls (+ VecExpand / AddColSum / VecAddColSum) by
+ * one launch over all instances (gemm_shared.hip; forward / backward with rows*in*out >= 2^28 at 16-byte aligned
+ * windows instead loop over tnet_affine_fwd / tnet_sgemm per window inside the entry point, which measured faster
+ * there: profiles/shared_linearity.json).  Any rows / in / out; window origins need no 16-byte
+ * alignment (pointers 4-byte aligned, strides multiples of 4 elements).
+ * TNET_ERR_ARG before any launch: n_inst < 1, dimensions that do not fit (dX.cols != n_inst*dW.rows, ...),
+ * a stride that is no multiple of 4, W or corrW overlapping X / E / Y / Eo.
+ *   tnet_shared_fwd    : Y_i  = X_i W + b                                        (cuSharedLinearity.cc:12-26)
+ *   tnet_shared_bwd    : Eo_i = E_i W^T  (beta 0)                                (cuSharedLinearity.cc:31-37)
+ *   tnet_shared_update : c  = sum_i X_i^T E_i + mmt*corrW ; corrW = c ; W += scale*c ; W += l2*W
+ *                        cb = sum_i colsum(E_i) + mmt*corr_b ; corr_b = cb ; b += scale*cb
+ *                        (cuSharedLinearity.cc:65-94 with tnet_affine_update's arithmetic; the caller computes
+ *                        scale = -lr/N and l2 = -lr*wc).  The reduction over n_inst*rows is cut into slices whose
+ *                        partial products are added in a fixed order (no atomics: the same bits every run;
+ *                        bias gradient fp32 inside a 32-row slab, fp64 across slabs and instances), in a
+ *                        per-stream workspace the library keeps.  corrW / corr_b may be NULL when mmt == 0. */
+int tnet_shared_fwd(const float* X, TnetMatrixDim dX, const float* W, TnetMatrixDim dW, const float* b, int n_inst,
+                    float* Y, TnetMatrixDim dY, void* stream);
+int tnet_shared_bwd(const float* E, TnetMatrixDim dE, const float* W, TnetMatrixDim dW, int n_inst, float* Eo,
+                    TnetMatrixDim dEo, void* stream);
+int tnet_shared_update(const float* X, TnetMatrixDim dX, const float* E, TnetMatrixDim dE, int n_inst, float* W,
+                       TnetMatrixDim dW, float* corrW, int ldcorr, float* b, float* corr_b, float scale, float mmt,
+                       float l2, void* stream);
+
 /* ---- per-element HybridTaus random numbers (CuRand, curand.tcc / curandkernels.cu) ----------
  * z1..z4: four uint32 state arrays with the element layout of the target matrix (index =
  * col + row*stride), seeded by the caller with lrand48() values > 128 (curand.tcc:36-45) and

@@ -210,6 +210,12 @@ int tnet_rnn_trainer_free(TnetRnnTrainer* t);
 int tnet_rnn_trainer_utterance(TnetRnnTrainer* t, const float* feats, int rows, int cols, int ld, const int* labels);
 long tnet_rnn_trainer_frames(TnetRnnTrainer* t);
 
+/* ---- <sharedlinearity> (CuSharedLinearity, cuSharedLinearity.cc) --------------------------------
+ * parameters of component i: W [in/N x out/N] (host row-major), bias [out/N], the instance count N; any
+ * pointer may be NULL.  tnet_net_get_params / tnet_net_set_params stay <biasedlinearity>-only. */
+int tnet_net_shared_get(TnetNetwork* net, int i, float* W, float* b, int* n_inst);
+int tnet_net_shared_set(TnetNetwork* net, int i, const float* W, const float* b);
+
 /* ---- data parallel (no reference counterpart: Platform.h:143-391 is the CPU analogue) ---- */
 int tnet_comm_unique_id(char out[128]);        /* rank 0 creates, the launcher broadcasts it */
 TnetComm* tnet_comm_create(int rank, int world, const char id[128]);

@@ -1,0 +1,3 @@
+// cuBlockArray.h -- drop-in header name of the reference (src/CuTNetLib/cuBlockArray.h): the MI355X CuTNetLib API lives in cushared.h.
+#pragma once
+#include "../host/cushared.h"

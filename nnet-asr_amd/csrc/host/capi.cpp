@@ -8,6 +8,7 @@
 #include "tnet_train.h"
 #include "curbm.h"
 #include "curecurrent.h"
+#include "cushared.h"
 #include "htkio.h"
 #include "trainer.h"
 
@@ -646,6 +647,28 @@ long tnet_rbm_trainer_prefill(TnetRbmTrainer* t, const float* feats, int rows, i
 }
 int tnet_rbm_trainer_replay(TnetRbmTrainer* t, long n) {
   TRY_BEGIN t->t->Replay(n);
+  TRY_END
+}
+
+// ----------------------------------------------------------------------- <sharedlinearity>
+static CuSharedLinearity& shared_layer(TnetNetwork* h, int i) {
+  if (i < 0 || i >= h->net.Layers()) Error("component index out of range");
+  auto* p = dynamic_cast<CuSharedLinearity*>(&h->net.Layer(i));
+  if (!p) Error("component is not <sharedlinearity>");
+  return *p;
+}
+int tnet_net_shared_get(TnetNetwork* h, int i, float* W, float* b, int* n_inst) {
+  TRY_BEGIN CuSharedLinearity& L = shared_layer(h, i);
+  if (W) L.Linearity().CopyToHost(W, L.Linearity().Cols());
+  if (b) L.Bias().CopyToHost(b);
+  if (n_inst) *n_inst = L.NInstances();
+  TRY_END
+}
+int tnet_net_shared_set(TnetNetwork* h, int i, const float* W, const float* b) {
+  TRY_BEGIN CuSharedLinearity& L = shared_layer(h, i);
+  if (W) L.Linearity().CopyFromHost(W, L.Linearity().Rows(), L.Linearity().Cols(), L.Linearity().Cols());
+  if (b) L.Bias().CopyFromHost(b, L.Bias().Dim());
+  CuDevice::Instantiate().Synchronize();
   TRY_END
 }
 

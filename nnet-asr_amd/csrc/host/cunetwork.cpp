@@ -4,6 +4,7 @@
 #include "cufeat.h"
 #include "curbm.h"
 #include "curecurrent.h"
+#include "cushared.h"
 
 #include <algorithm>
 #include <cctype>
@@ -159,6 +160,9 @@ CuComponent* CuNetwork::ComponentFactory(std::istream& rIn) {
   else if (tag == "<softmax>") pRet = new CuSoftmax(nInputs, nOutputs, pPred);
   else if (tag == "<rbm>") pRet = new CuRbm(nInputs, nOutputs, pPred);
   else if (tag == "<recurrent>") pRet = new CuRecurrent(nInputs, nOutputs, pPred);
+  // convolutive-bottleneck / universal-context layers (cuNetwork.cc:286, 303)
+  else if (tag == "<sharedlinearity>") pRet = new CuSharedLinearity(nInputs, nOutputs, pPred);
+  else if (tag == "<blockarray>") pRet = new CuBlockArray(nInputs, nOutputs, pPred);
   // feature front end (cuNetwork.cc:263-268, cuCRBEDctFeat.h)
   else if (tag == "<expand>") pRet = new CuExpand(nInputs, nOutputs, pPred);
   else if (tag == "<copy>") pRet = new CuCopy(nInputs, nOutputs, pPred);

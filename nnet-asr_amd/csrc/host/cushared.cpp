@@ -1,0 +1,207 @@
+// cushared.cpp -- <sharedlinearity> on the instance-batched gfx950 kernels, and <blockarray>.
+#include "cushared.h"
+
+#include <algorithm>
+#include <cctype>
+
+#include "culayers.h"
+#include "cunetwork.h"
+
+namespace TNet {
+
+#define S ((void*)CuDevice::Instantiate().Stream())
+
+// ------------------------------------------------------------------------- CuSharedLinearity
+void CuSharedLinearity::PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  CuProfileScope p("CuSharedLinearity::Propagate");
+  // Y_i = b + X_i W for every instance (VecExpand + AddScaledRow + N OffsetGemm('N','N'),
+  // cuSharedLinearity.cc:12-26) in one launch
+  KTScope kt("shared_fwd:" + std::to_string(mNInstances) + "x" + std::to_string(mLinearity.Rows()) + "x" +
+                 std::to_string(mLinearity.Cols()),
+             2.0 * X.Rows() * GetNInputs() * mLinearity.Cols());
+  TNET_SAFE_CALL(tnet_shared_fwd(X.pCUData(), X.Dim(), mLinearity.pCUData(), mLinearity.Dim(), mBias.pCUData(),
+                                 mNInstances, Y.pCUData(), Y.Dim(), S));
+}
+
+void CuSharedLinearity::BackpropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  CuProfileScope p("CuSharedLinearity::Backpropagate");
+  // Y_i = X_i W^T with beta 0 (N OffsetGemm('N','T'), cuSharedLinearity.cc:31-37) in one launch
+  KTScope kt("shared_bwd:" + std::to_string(mNInstances) + "x" + std::to_string(mLinearity.Rows()) + "x" +
+                 std::to_string(mLinearity.Cols()),
+             2.0 * X.Rows() * GetNInputs() * mLinearity.Cols());
+  TNET_SAFE_CALL(tnet_shared_bwd(X.pCUData(), X.Dim(), mLinearity.pCUData(), mLinearity.Dim(), mNInstances,
+                                 Y.pCUData(), Y.Dim(), S));
+}
+
+void CuSharedLinearity::UpdateConstants(size_t rows, float* scale, float* l2) const {
+  // cuSharedLinearity.cc:67-75, 89-93
+  BaseFloat N = 1;
+  if (mGradDivFrm) N = static_cast<BaseFloat>(rows);
+  BaseFloat mmt_gain = static_cast<BaseFloat>(1.0 / (1.0 - mMomentum));
+  N *= mmt_gain;
+  N *= static_cast<BaseFloat>(mNInstances);  // the gradient is a sum over the instances
+  *scale = -mLearningRate / N;
+  *l2 = -mLearningRate * mWeightcost;
+}
+
+void CuSharedLinearity::Update() {
+  CuProfileScope p("CuSharedLinearity::Update");
+  const CuMatrix<BaseFloat>& X = GetInput();
+  const CuMatrix<BaseFloat>& E = GetErrorInput();
+  float scale, l2;
+  UpdateConstants(X.Rows(), &scale, &l2);
+  const bool mmt = mMomentum != 0.0f;
+  // gradient over all instances, bias gradient and the SGD apply in one call; with momentum 0 the
+  // correction buffers are never read, so they are not written either
+  KTScope kt("shared_upd:" + std::to_string(mNInstances) + "x" + std::to_string(mLinearity.Rows()) + "x" +
+                 std::to_string(mLinearity.Cols()),
+             2.0 * X.Rows() * GetNInputs() * mLinearity.Cols());
+  TNET_SAFE_CALL(tnet_shared_update(X.pCUData(), X.Dim(), E.pCUData(), E.Dim(), mNInstances, mLinearity.pCUData(),
+                                    mLinearity.Dim(), mmt ? mLinearityCorrection.pCUData() : nullptr,
+                                    (int)mLinearityCorrection.Stride(), mBias.pCUData(),
+                                    mmt ? mBiasCorrection.pCUData() : nullptr, scale, mMomentum, l2, S));
+}
+
+void CuSharedLinearity::ReadFromStream(std::istream& rIn) {
+  // number of instances, then the matrix stored transposed as SNet does, then the bias
+  // (cuSharedLinearity.cc:99-157)
+  mNInstances = 0;
+  rIn >> std::ws >> mNInstances;
+  if (rIn.fail() || mNInstances < 1) {
+    std::ostringstream os;
+    os << "Bad number of instances:" << mNInstances;
+    Error(os.str());
+  }
+  if (GetNInputs() % mNInstances != 0 || GetNOutputs() % mNInstances != 0) {
+    std::ostringstream os;
+    os << "Number of Inputs/Outputs must be divisible by number of instances"
+       << " Inputs:" << GetNInputs() << " Outputs" << GetNOutputs() << " Intances:" << mNInstances;
+    Error(os.str());
+  }
+  BfMatrix transpose;
+  ReadMatrixFast(rIn, transpose);
+  BfVector bias;
+  ReadVectorFast(rIn, bias);
+  if (transpose.Cols() * transpose.Rows() == 0) Error("Missing linearity matrix in network file");
+  if (bias.Dim() == 0) Error("Missing bias vector in network file");
+  if (transpose.Rows() != GetNOutputs() / mNInstances || transpose.Cols() != GetNInputs() / mNInstances ||
+      bias.Dim() != GetNOutputs() / mNInstances) {
+    std::ostringstream os;
+    os << "Wrong dimensionalities of matrix/vector in network file\n"
+       << "Inputs:" << GetNInputs() << "Outputs:" << GetNOutputs() << "\n"
+       << "linearityCols:" << transpose.Rows() << "linearityRows:" << transpose.Cols() << "biasDims:" << bias.Dim()
+       << "\n";
+    Error(os.str());
+  }
+  mLinearity.CopyFrom(BfMatrix(transpose, TRANS));
+  mBias.CopyFrom(bias);
+  mLinearityCorrection.Init(mLinearity.Rows(), mLinearity.Cols());
+  mBiasCorrection.Init(mBias.Dim());
+}
+
+void CuSharedLinearity::WriteToStream(std::ostream& rOut) {
+  rOut << mNInstances << std::endl;
+  BfMatrix tmp;
+  mLinearity.CopyTo(tmp);
+  BfMatrix transpose(tmp, TRANS);
+  rOut << transpose;
+  BfVector vec;
+  mBias.CopyTo(vec);
+  rOut << vec;
+  rOut << std::endl;
+}
+
+// ------------------------------------------------------------------------------ CuBlockArray
+CuBlockArray::~CuBlockArray() {
+  for (auto* n : mBlocks) delete n;
+  for (auto* m : mStripeIn) delete m;
+  for (auto* m : mStripeOut) delete m;
+}
+
+void CuBlockArray::PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  CuProfileScope p("CuBlockArray::Propagate");
+  // each block on its column stripe of X, its output into its stripe of Y (cuBlockArray.cc:10-38); the
+  // stripes are copied (any origin, 4-byte granularity), so a block's kernels see aligned matrices
+  size_t x_ori = 0, y_ori = 0;
+  for (int i = 0; i < mNBlocks; i++) {
+    const size_t nx = mBlocks[i]->GetNInputs(), ny = mBlocks[i]->GetNOutputs();
+    CuMatrix<BaseFloat>& colsX = *mStripeIn[i];
+    CuMatrix<BaseFloat>& colsY = *mStripeOut[i];
+    colsX.Init(X.Rows(), nx);
+    colsX.CopyCols(nx, x_ori, X, 0);
+    mBlocks[i]->Propagate(colsX, colsY);
+    Y.CopyCols(ny, 0, colsY, y_ori);
+    x_ori += nx;
+    y_ori += ny;
+  }
+}
+
+void CuBlockArray::BackpropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  (void)X;
+  (void)Y;
+  Error("CuBlockArray::Backpropagate: Unimplemented");  // cuBlockArray.cc:41-46
+}
+
+void CuBlockArray::Update() { Error("CuBlockArray::Update: Unimplemented"); }  // cuBlockArray.cc:49-54
+
+void CuBlockArray::ReadFromStream(std::istream& rIn) {
+  // cuBlockArray.cc:57-122
+  if (!mBlocks.empty()) {
+    std::ostringstream os;
+    os << "Cannot read block vector, aleady filled bt " << mBlocks.size() << "elements";
+    Error(os.str());
+  }
+  mNBlocks = 0;
+  rIn >> std::ws >> mNBlocks;
+  if (rIn.fail() || mNBlocks < 1) {
+    std::ostringstream os;
+    os << "Bad number of blocks:" << mNBlocks;
+    Error(os.str());
+  }
+  for (int i = 0; i < mNBlocks; i++) {
+    std::string tag;
+    rIn >> std::ws >> tag;
+    std::transform(tag.begin(), tag.end(), tag.begin(), ::tolower);
+    if (tag != "<block>") Error("<block> keywotd expected");
+    int block_id = 0;
+    rIn >> std::ws >> block_id;
+    if (rIn.fail() || block_id != i + 1) {
+      std::ostringstream os;
+      os << "Expected block number:" << i + 1 << " read block number: " << block_id;
+      Error(os.str());
+    }
+    std::unique_ptr<CuNetwork> nnet(new CuNetwork);
+    nnet->ReadNetwork(rIn);  // up to this block's <endblock>
+    if (nnet->Layers() == 0) Error("Cannot read empty network to a block");
+    mBlocks.push_back(nnet.release());
+    mStripeIn.push_back(new CuMatrix<BaseFloat>());
+    mStripeOut.push_back(new CuMatrix<BaseFloat>());
+  }
+  size_t sum_inputs = 0, sum_outputs = 0;
+  for (auto* b : mBlocks) {
+    sum_inputs += b->GetNInputs();
+    sum_outputs += b->GetNOutputs();
+  }
+  if (sum_inputs != GetNInputs()) {
+    std::ostringstream os;
+    os << "Non-matching number of INPUTS! Declared:" << GetNInputs() << " summed from blocks" << sum_inputs;
+    Error(os.str());
+  }
+  if (sum_outputs != GetNOutputs()) {
+    std::ostringstream os;
+    os << "Non-matching number of OUTPUTS! Declared:" << GetNOutputs() << " summed from blocks" << sum_outputs;
+    Error(os.str());
+  }
+}
+
+void CuBlockArray::WriteToStream(std::ostream& rOut) {
+  // cuBlockArray.cc:125-135
+  rOut << " " << mBlocks.size() << " ";
+  for (size_t i = 0; i < mBlocks.size(); i++) {
+    rOut << "<block> " << i + 1 << "\n";
+    mBlocks[i]->WriteNetwork(rOut);
+    rOut << "<endblock>\n";
+  }
+}
+
+}  // namespace TNet

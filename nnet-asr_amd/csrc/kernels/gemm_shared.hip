@@ -1,0 +1,452 @@
+// gemm_shared.hip -- instance-batched GEMMs of <sharedlinearity> (src/CuTNetLib/cuSharedLinearity.cc:10-96).
+//
+// One weight matrix W [in x out] is applied to the N column windows X_i = X[:, i*in : (i+1)*in] of the input.
+// The reference runs N OffsetGemm calls per direction (+ VecExpand / AddColSum / VecAddColSum); here each
+// direction is one launch over all instances:
+//   tnet_shared_fwd    Y_i  = X_i W + b                      flat grid over (instance, tile-row, tile-col)
+//   tnet_shared_bwd    Eo_i = E_i W^T                         the same grid
+//   tnet_shared_update G    = sum_i X_i^T E_i, colsum(E) and the SGD apply: the reduction depth N*rows is cut
+//                      into (instance, row-chunk) slices whose partial products go to a per-stream workspace;
+//                      a second launch adds them in slice order (no atomics: same bits every run) and applies
+//                      the project's fused SGD arithmetic (gemm_f32.hip EPI_SGD) to W and b.
+//
+// (One shape class -- a single instance's product already filling the GPU, at aligned windows -- runs forward and
+// backward as a per-window loop over the library's tuned GEMM inside the entry points: loop_class below.)
+//
+// All three run one tile kernel on v_mfma_f32_16x16x4_f32 (fp32 in / fp32 accumulate): 256 threads = 2 x 2
+// waves, a 64x64 or 128x128 output tile, k-tiles of 16 staged through a double-buffered LDS image
+// [k][m or n] (row pitch tile + 16 floats: the four k rows a wave's MFMA operand read touches fall on disjoint
+// banks), the next k-tile's global loads in flight while the current one is multiplied.  An operand is read
+// with 16-byte loads when its pointer, window origins and stride allow it and through a masked scalar path
+// otherwise (in = 39 puts every window origin off 16 bytes); rows, in and out need no tile multiple:
+// out-of-range elements are never read (they enter the product as zeros) and never stored.
+#include "kcommon.h"
+
+#include <map>
+#include <mutex>
+
+namespace tnetk {
+namespace {
+
+constexpr int kBK = 16;       // k-tile depth
+constexpr int kThreads = 256; // 2 x 2 waves
+constexpr int kSlab = 32;     // rows whose column sum stays in fp32 (the project's slab size)
+
+enum { MODE_FWD = 0, MODE_BWD = 1, MODE_UPD = 2 };
+
+struct SharedP {
+  const float* A; long lda; int a_step;  // A operand: base, row stride, per-instance column origin step
+  const float* B; long ldb; int b_step;
+  float* C; long ldc; int c_step;        // output (fwd / bwd): per-instance column origin step
+  const float* bias;                     // fwd
+  int M, N, K;                           // one instance's GEMM
+  int tn, tiles;                         // tile columns, tiles per instance (or per slice)
+  int vecA, vecB;                        // 16-byte loads allowed
+  // update only
+  int kchunk, kslices;                   // rows per K slice (a multiple of kSlab), slices per instance
+  float* part; long ldp, pslab;          // partial products [n_inst * kslices][M][ldp]
+  double* bpart; long ldbp;              // partial column sums of E [n_inst * kslices][ldbp]
+};
+
+// One thread's share of a [BMN x 16] operand tile: BMN / 64 groups of four elements.
+//   KC (k contiguous in memory: elem(mn, k) = base[mn * ld + k]): the four are consecutive k of one row
+//   MC (mn contiguous:          elem(mn, k) = base[k * ld + mn]): the four are consecutive mn of one k row
+template <int BMN, bool KC>
+__device__ __forceinline__ void tile_coord(int r, int& mn, int& k) {
+  const int e = (int)threadIdx.x + kThreads * r;
+  if (KC) {
+    mn = e >> 2;
+    k = (e & 3) * 4;
+  } else {
+    k = e / (BMN / 4);
+    mn = (e % (BMN / 4)) * 4;
+  }
+}
+
+template <int BMN, bool KC>
+__device__ __forceinline__ void load_tile(const float* __restrict__ base, long ld, int mn0, int MN, int k0, int K,
+                                          int vec, f32x4 (&v)[BMN / 64]) {
+#pragma unroll
+  for (int r = 0; r < BMN / 64; ++r) {
+    int mn, k;
+    tile_coord<BMN, KC>(r, mn, k);
+    const int gmn = mn0 + mn, gk = k0 + k;
+    f32x4 x = {0.f, 0.f, 0.f, 0.f};
+    if (KC) {
+      if (gmn < MN && gk < K) {
+        const float* q = base + (long)gmn * ld + gk;
+        if (vec && gk + 3 < K) {
+          x = *(const f32x4*)q;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (gk + j < K) x[j] = q[j];
+        }
+      }
+    } else {
+      if (gk < K && gmn < MN) {
+        const float* q = base + (long)gk * ld + gmn;
+        if (vec && gmn + 3 < MN) {
+          x = *(const f32x4*)q;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (gmn + j < MN) x[j] = q[j];
+        }
+      }
+    }
+    v[r] = x;
+  }
+}
+
+template <int BMN, bool KC>
+__device__ __forceinline__ void store_tile(float* __restrict__ s, const f32x4 (&v)[BMN / 64]) {
+  constexpr int S = BMN + 16;
+#pragma unroll
+  for (int r = 0; r < BMN / 64; ++r) {
+    int mn, k;
+    tile_coord<BMN, KC>(r, mn, k);
+    if (KC) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[(k + j) * S + mn] = v[r][j];
+    } else {
+      *(f32x4*)&s[k * S + mn] = v[r];
+    }
+  }
+}
+
+// T: 16x16 MFMA tiles per wave and dimension (2: 64x64 workgroup tile, 4: 128x128)
+template <int MODE, int T>
+__global__ __launch_bounds__(kThreads) void shared_gemm_kernel(const SharedP p) {
+  constexpr int BT = 32 * T;     // workgroup tile edge
+  constexpr int S = BT + 16;     // LDS row pitch
+  constexpr bool A_KC = MODE != MODE_UPD, B_KC = MODE == MODE_BWD;
+  __shared__ __attribute__((aligned(16))) float sA[2][kBK * S];
+  __shared__ __attribute__((aligned(16))) float sB[2][kBK * S];
+
+  // blockIdx -> (instance or slice, tile-row, tile-col): one instance's tiles are consecutive
+  const int z = (int)blockIdx.x / p.tiles, rem = (int)blockIdx.x % p.tiles;
+  const int bm = (rem / p.tn) * BT, bn = (rem % p.tn) * BT;
+  int inst = z, K = p.K;
+  long krow0 = 0;
+  if (MODE == MODE_UPD) {
+    inst = z / p.kslices;
+    krow0 = (long)(z % p.kslices) * p.kchunk;
+    K = min(p.kchunk, p.K - (int)krow0);
+  }
+  // window bases: KC operands index [mn][k] from `base`, MC operands [k][mn]
+  const float* A = p.A + (long)inst * p.a_step + (A_KC ? 0 : krow0 * p.lda);
+  const float* B = p.B + (long)inst * p.b_step + (B_KC ? 0 : krow0 * p.ldb);
+
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  const int wm = (wave >> 1) * 16 * T, wn = (wave & 1) * 16 * T;
+  const int l15 = lane & 15, lk = lane >> 4;
+
+  f32x4 acc[T][T];
+#pragma unroll
+  for (int a = 0; a < T; ++a)
+#pragma unroll
+    for (int b = 0; b < T; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // update: the first tile-row's workgroups also sum the columns of their E tile (thread c: column bn + c):
+  // fp32 inside a 32-row slab, fp64 across slabs
+  const bool colsum = MODE == MODE_UPD && bm == 0 && (int)threadIdx.x < BT;
+  float cs = 0.f;
+  double cd = 0.0;
+
+  f32x4 ra[BT / 64], rb[BT / 64];
+  const int nk = (K + kBK - 1) / kBK;
+  load_tile<BT, A_KC>(A, p.lda, bm, p.M, 0, K, p.vecA, ra);
+  load_tile<BT, B_KC>(B, p.ldb, bn, p.N, 0, K, p.vecB, rb);
+  store_tile<BT, A_KC>(sA[0], ra);
+  store_tile<BT, B_KC>(sB[0], rb);
+  __syncthreads();
+  for (int kt = 0; kt < nk; ++kt) {
+    const int buf = kt & 1;
+    if (kt + 1 < nk) {
+      load_tile<BT, A_KC>(A, p.lda, bm, p.M, (kt + 1) * kBK, K, p.vecA, ra);
+      load_tile<BT, B_KC>(B, p.ldb, bn, p.N, (kt + 1) * kBK, K, p.vecB, rb);
+    }
+    const float* a_s = sA[buf];
+    const float* b_s = sB[buf];
+#pragma unroll
+    for (int s = 0; s < kBK / 4; ++s) {
+      const int kk = s * 4 + lk;
+      float av[T], bv[T];
+#pragma unroll
+      for (int a = 0; a < T; ++a) av[a] = a_s[kk * S + wm + a * 16 + l15];
+#pragma unroll
+      for (int b = 0; b < T; ++b) bv[b] = b_s[kk * S + wn + b * 16 + l15];
+#pragma unroll
+      for (int a = 0; a < T; ++a)
+#pragma unroll
+        for (int b = 0; b < T; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[a][b], 0, 0, 0);
+    }
+    if (MODE == MODE_UPD) {
+      if (colsum) {
+#pragma unroll
+        for (int k = 0; k < kBK; ++k) cs += b_s[k * S + (int)threadIdx.x];
+        if ((kt & (kSlab / kBK - 1)) == kSlab / kBK - 1) {
+          cd += (double)cs;
+          cs = 0.f;
+        }
+      }
+    }
+    if (kt + 1 < nk) {  // the other buffer: last read before the barrier that ended iteration kt - 1
+      store_tile<BT, A_KC>(sA[buf ^ 1], ra);
+      store_tile<BT, B_KC>(sB[buf ^ 1], rb);
+    }
+    __syncthreads();
+  }
+
+  // epilogue: accumulator register r of MFMA tile (a, b) is row 4 * (lane >> 4) + r, column lane & 15
+  if (MODE == MODE_UPD) {
+    float* P = p.part + (long)z * p.pslab;
+#pragma unroll
+    for (int a = 0; a < T; ++a)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = bm + wm + a * 16 + lk * 4 + r;
+        if (row >= p.M) continue;
+#pragma unroll
+        for (int b = 0; b < T; ++b) {
+          const int col = bn + wn + b * 16 + l15;
+          if (col < p.N) P[(long)row * p.ldp + col] = acc[a][b][r];
+        }
+      }
+    if (colsum) {
+      cd += (double)cs;
+      const int col = bn + (int)threadIdx.x;
+      if (col < p.N) p.bpart[(long)z * p.ldbp + col] = cd;
+    }
+  } else {
+    float* C = p.C + (long)inst * p.c_step;
+    float bias_v[T];
+#pragma unroll
+    for (int b = 0; b < T; ++b) {
+      const int col = bn + wn + b * 16 + l15;
+      bias_v[b] = (MODE == MODE_FWD && col < p.N) ? p.bias[col] : 0.f;
+    }
+#pragma unroll
+    for (int a = 0; a < T; ++a)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = bm + wm + a * 16 + lk * 4 + r;
+        if (row >= p.M) continue;
+#pragma unroll
+        for (int b = 0; b < T; ++b) {
+          const int col = bn + wn + b * 16 + l15;
+          if (col < p.N) C[(long)row * p.ldc + col] = MODE == MODE_FWD ? acc[a][b][r] + bias_v[b] : acc[a][b][r];
+        }
+      }
+  }
+}
+
+// The update's second launch.  Element (row, col) of W: the slices' partial products added in slice order
+// (instance-major, then row-chunk), then corr = g + mmt*corr ; W += scale*corr ; W += l2*W (EPI_SGD's
+// arithmetic).  The last N threads: the bias, its gradient the slices' column sums added in fp64 in the same
+// order, corr_b = g + mmt*corr_b ; b += scale*corr_b (bias_pre_finish's arithmetic).
+__global__ __launch_bounds__(kThreads) void shared_combine_kernel(const float* __restrict__ P, long pslab, long ldp,
+                                                                  const double* __restrict__ bpart, long ldbp, int Z,
+                                                                  int M, int N, float* __restrict__ W, long ldw,
+                                                                  float* __restrict__ corr, long ldcorr,
+                                                                  float* __restrict__ b, float* __restrict__ corr_b,
+                                                                  float scale, float mmt, float l2) {
+  const long idx = (long)blockIdx.x * kThreads + threadIdx.x, nw = (long)M * N;
+  if (idx < nw) {
+    const int row = (int)(idx / N), col = (int)(idx % N);
+    const float* q = P + (long)row * ldp + col;
+    float g = q[0];
+    for (int z = 1; z < Z; ++z) g += q[(long)z * pslab];
+    float c = g;
+    if (corr) {
+      float* qp = corr + (long)row * ldcorr + col;
+      c = g + mmt * *qp;
+      *qp = c;
+    }
+    float* wp = W + (long)row * ldw + col;
+    float w = *wp;
+    w = w + scale * c;
+    w = w + l2 * w;
+    *wp = w;
+  } else if (idx < nw + N) {
+    const int col = (int)(idx - nw);
+    double s = 0.0;
+    for (int z = 0; z < Z; ++z) s += bpart[(long)z * ldbp + col];
+    float g = (float)s;
+    if (corr_b) {
+      g = g + mmt * corr_b[col];
+      corr_b[col] = g;
+    }
+    b[col] = b[col] + scale * g;
+  }
+}
+
+// per-stream workspace of the update's partial products (grown on demand, reused launch after launch: the
+// library enqueues a stream's work in order -- gemm_f32.hip's split-K workspace has the same rule)
+std::mutex g_ws_mu;
+std::map<hipStream_t, std::pair<void*, size_t>> g_ws;
+void* shared_workspace(size_t bytes, hipStream_t st) {
+  std::lock_guard<std::mutex> lk(g_ws_mu);
+  auto& w = g_ws[st];
+  if (bytes > w.second) {
+    if (w.first) {
+      if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
+      (void)hipFree(w.first);
+      w = {nullptr, 0};
+    }
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) return nullptr;
+    w = {q, bytes};
+  }
+  return w.first;
+}
+
+bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+bool aligned4(const void* q) { return ((uintptr_t)q & 3) == 0; }
+bool dim_ok(const void* q, TnetMatrixDim d) {
+  return q && aligned4(q) && d.rows >= 0 && d.cols >= 1 && d.stride >= d.cols && (d.stride & 3) == 0;
+}
+bool overlap(const void* a, TnetMatrixDim da, const void* b, TnetMatrixDim db) {
+  if (!a || !b || da.rows <= 0 || db.rows <= 0) return false;
+  const char *a0 = (const char*)a, *b0 = (const char*)b;
+  const size_t na = (size_t)da.rows * (size_t)da.stride * 4, nb = (size_t)db.rows * (size_t)db.stride * 4;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+// 16-byte loads of an operand whose windows start `step` columns apart: the base and every origin aligned
+// (the strides are multiples of 4 by the entry points' argument checks)
+int vec_ok(const void* q, int step, int n_inst) { return aligned16(q) && (n_inst == 1 || (step & 3) == 0); }
+
+// 128x128 tiles where they still give every CU a workgroup, else 64x64
+int pick_tile(int M, int N, long batch) {
+  const long big = (long)cdiv(M, 128) * cdiv(N, 128) * batch;
+  return big >= 200 ? 4 : 2;
+}
+
+// Shape class routed to the per-instance loop (measured, tools/shared_bench.py / profiles/shared_linearity.json):
+// where one instance's product alone fills the GPU (rows * in * out >= 2^28 multiply-adds, e.g. bunch 1024,
+// 440 -> 1024) the library's tuned single-GEMM kernels in a loop beat this file's tile kernel forward and
+// backward (0.97x / 0.86x), so those calls go to tnet_affine_fwd / tnet_sgemm per window -- possible only
+// where every window is 16-byte aligned.  Below that size, at unaligned windows and for the update the batched
+// launch is the faster one (1.4x - 11x).
+bool loop_class(long M, long N, long K, int n_in, int n_out, const void* a, const void* w, const void* c) {
+  return M * N * K >= (1L << 28) && ((n_in | n_out) & 3) == 0 && aligned16(a) && aligned16(w) && aligned16(c);
+}
+
+template <int MODE>
+int launch_tiles(SharedP& p, long batch, hipStream_t st) {
+  const int T = pick_tile(p.M, p.N, batch), bt = 32 * T;
+  p.tn = cdiv(p.N, bt);
+  p.tiles = cdiv(p.M, bt) * p.tn;
+  const long grid = (long)p.tiles * batch;
+  if (grid <= 0 || grid > 0x7fffffffL) return TNET_ERR_ARG;
+  if (T == 4) shared_gemm_kernel<MODE, 4><<<(unsigned)grid, kThreads, 0, st>>>(p);
+  else shared_gemm_kernel<MODE, 2><<<(unsigned)grid, kThreads, 0, st>>>(p);
+  TNET_LAUNCH_CHECK();
+  return TNET_OK;
+}
+
+}  // namespace
+}  // namespace tnetk
+
+using namespace tnetk;
+
+extern "C" int tnet_shared_fwd(const float* X, TnetMatrixDim dX, const float* W, TnetMatrixDim dW, const float* b,
+                               int n_inst, float* Y, TnetMatrixDim dY, void* stream) {
+  if (n_inst < 1 || !dim_ok(X, dX) || !dim_ok(W, dW) || !dim_ok(Y, dY) || !b || !aligned4(b) || dW.rows < 1 ||
+      (long)dX.cols != (long)n_inst * dW.rows || (long)dY.cols != (long)n_inst * dW.cols || dY.rows != dX.rows)
+    return TNET_ERR_ARG;
+  if (overlap(W, dW, X, dX) || overlap(W, dW, Y, dY) || overlap(X, dX, Y, dY)) return TNET_ERR_ARG;
+  if (dX.rows == 0) return TNET_OK;
+  if (loop_class(dX.rows, dW.cols, dW.rows, dW.rows, dW.cols, X, W, Y) && aligned16(b)) {
+    for (int i = 0; i < n_inst; ++i) {
+      const int rc = tnet_affine_fwd(X + (long)i * dW.rows, TnetMatrixDim{dX.rows, dW.rows, dX.stride}, W, dW, b,
+                                     Y + (long)i * dW.cols, TnetMatrixDim{dX.rows, dW.cols, dY.stride}, 0, stream);
+      if (rc) return rc;
+    }
+    return TNET_OK;
+  }
+  SharedP p{};
+  p.A = X; p.lda = dX.stride; p.a_step = dW.rows;
+  p.B = W; p.ldb = dW.stride; p.b_step = 0;
+  p.C = Y; p.ldc = dY.stride; p.c_step = dW.cols;
+  p.bias = b;
+  p.M = dX.rows; p.N = dW.cols; p.K = dW.rows;
+  p.vecA = vec_ok(X, dW.rows, n_inst);
+  p.vecB = vec_ok(W, 0, 1);
+  return launch_tiles<MODE_FWD>(p, n_inst, (hipStream_t)stream);
+}
+
+extern "C" int tnet_shared_bwd(const float* E, TnetMatrixDim dE, const float* W, TnetMatrixDim dW, int n_inst,
+                               float* Eo, TnetMatrixDim dEo, void* stream) {
+  if (n_inst < 1 || !dim_ok(E, dE) || !dim_ok(W, dW) || !dim_ok(Eo, dEo) || dW.rows < 1 ||
+      (long)dE.cols != (long)n_inst * dW.cols || (long)dEo.cols != (long)n_inst * dW.rows || dEo.rows != dE.rows)
+    return TNET_ERR_ARG;
+  if (overlap(W, dW, E, dE) || overlap(W, dW, Eo, dEo) || overlap(E, dE, Eo, dEo)) return TNET_ERR_ARG;
+  if (dE.rows == 0) return TNET_OK;
+  if (loop_class(dE.rows, dW.rows, dW.cols, dW.rows, dW.cols, E, W, Eo)) {
+    for (int i = 0; i < n_inst; ++i) {
+      const int rc = tnet_sgemm('N', 'T', dE.rows, dW.rows, dW.cols, 1.f, E + (long)i * dW.cols, dE.stride, W,
+                                dW.stride, 0.f, Eo + (long)i * dW.rows, dEo.stride, stream);
+      if (rc) return rc;
+    }
+    return TNET_OK;
+  }
+  SharedP p{};
+  p.A = E; p.lda = dE.stride; p.a_step = dW.cols;
+  p.B = W; p.ldb = dW.stride; p.b_step = 0;  // B[k][n] = W[n][k]: k contiguous
+  p.C = Eo; p.ldc = dEo.stride; p.c_step = dW.rows;
+  p.M = dE.rows; p.N = dW.rows; p.K = dW.cols;
+  p.vecA = vec_ok(E, dW.cols, n_inst);
+  p.vecB = vec_ok(W, 0, 1);
+  return launch_tiles<MODE_BWD>(p, n_inst, (hipStream_t)stream);
+}
+
+extern "C" int tnet_shared_update(const float* X, TnetMatrixDim dX, const float* E, TnetMatrixDim dE, int n_inst,
+                                  float* W, TnetMatrixDim dW, float* corrW, int ldcorr, float* b, float* corr_b,
+                                  float scale, float mmt, float l2, void* stream) {
+  if (n_inst < 1 || !dim_ok(X, dX) || !dim_ok(E, dE) || !dim_ok(W, dW) || !b || !aligned4(b) || dW.rows < 1 ||
+      (long)dX.cols != (long)n_inst * dW.rows || (long)dE.cols != (long)n_inst * dW.cols || dE.rows != dX.rows)
+    return TNET_ERR_ARG;
+  if (corrW && (!aligned4(corrW) || ldcorr < dW.cols || (ldcorr & 3))) return TNET_ERR_ARG;
+  if (corr_b && !aligned4(corr_b)) return TNET_ERR_ARG;
+  if ((!corrW || !corr_b) && mmt != 0.f) return TNET_ERR_ARG;  // nullable only where they are never read
+  const TnetMatrixDim dC{dW.rows, dW.cols, ldcorr};
+  if (overlap(W, dW, X, dX) || overlap(W, dW, E, dE) || overlap(corrW, dC, X, dX) || overlap(corrW, dC, E, dE) ||
+      overlap(W, dW, corrW, dC))
+    return TNET_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = dX.rows;
+  SharedP p{};
+  p.A = X; p.lda = dX.stride; p.a_step = dW.rows;  // A[m][k] = X[k][i*in + m]: m contiguous
+  p.B = E; p.ldb = dE.stride; p.b_step = dW.cols;
+  p.M = dW.rows; p.N = dW.cols; p.K = rows;
+  p.vecA = vec_ok(X, dW.rows, n_inst);
+  p.vecB = vec_ok(E, dW.cols, n_inst);
+  // K slices: one per instance, and rows cut further (in multiples of the 32-row slab) until about two
+  // workgroups per CU are in flight
+  const int T = rows > 0 ? pick_tile(p.M, p.N, n_inst) : 2;
+  const long tiles = (long)cdiv(p.M, 32 * T) * cdiv(p.N, 32 * T);
+  int want = (int)std::min<long>(cdiv(512, tiles * n_inst), 64);
+  want = std::max(1, std::min(want, cdiv(std::max(rows, 1), kSlab)));
+  p.kchunk = cdiv(cdiv(std::max(rows, 1), want), kSlab) * kSlab;
+  p.kslices = cdiv(std::max(rows, 1), p.kchunk);
+  const long Z = (long)n_inst * p.kslices;
+  p.ldp = (p.N + 3) & ~3L;
+  p.pslab = (long)p.M * p.ldp;
+  p.ldbp = p.N;
+  const size_t bbytes = (((size_t)Z * p.ldbp * sizeof(double)) + 255) & ~(size_t)255;
+  char* ws = (char*)shared_workspace(bbytes + (size_t)Z * p.pslab * sizeof(float), st);
+  if (!ws) return TNET_ERR_RUNTIME;
+  p.bpart = (double*)ws;
+  p.part = (float*)(ws + bbytes);
+  // rows == 0: K = 0, every slice stores zeros (the SGD still applies momentum and weight decay)
+  int rc = launch_tiles<MODE_UPD>(p, Z, st);
+  if (rc) return rc;
+  const long n = (long)p.M * p.N + p.N;
+  shared_combine_kernel<<<(unsigned)cdiv(n, kThreads), kThreads, 0, st>>>(p.part, p.pslab, p.ldp, p.bpart, p.ldbp,
+                                                                          (int)Z, p.M, p.N, W, dW.stride, corrW, ldcorr,
+                                                                          b, corr_b, scale, mmt, l2);
+  TNET_LAUNCH_CHECK();
+  return TNET_OK;
+}

@@ -195,6 +195,26 @@ class Network:
         check(lib().tnet_net_recurrent_get(self.h, i, W.ctypes.data, b.ctypes.data), "recurrent_get")
         return W, b
 
+    def shared_params(self, i: int = 0):
+        """(W [n_in/N x n_out/N], bias [n_out/N], N) of a <sharedlinearity> component."""
+        _, ni, no = self.components()[i]
+        n = C.c_int()
+        check(lib().tnet_net_shared_get(self.h, i, None, None, C.byref(n)), "shared_get")
+        W = np.empty((ni // n.value, no // n.value), np.float32)
+        b = np.empty(no // n.value, np.float32)
+        check(lib().tnet_net_shared_get(self.h, i, W.ctypes.data, b.ctypes.data, None), "shared_get")
+        return W, b, n.value
+
+    def set_shared_params(self, i: int, W=None, b=None) -> None:
+        W = None if W is None else np.ascontiguousarray(W, np.float32)
+        b = None if b is None else np.ascontiguousarray(b, np.float32)
+        if W is not None or b is not None:
+            Wc, bc, _ = self.shared_params(i)
+            if (W is not None and W.shape != Wc.shape) or (b is not None and b.shape != bc.shape):
+                raise ValueError("set_shared_params: shape mismatch")
+        check(lib().tnet_net_shared_set(self.h, i, None if W is None else W.ctypes.data,
+                                        None if b is None else b.ctypes.data), "shared_set")
+
     def rbm_params(self, i: int = 0):
         """(W [n_vis x n_hid], vis_bias, hid_bias, (vis_type, hid_type)) of an <rbm> component."""
         _, ni, no = self.components()[i]

@@ -108,6 +108,10 @@ _SIGS = {
     "tnet_affine_update_bwd_pair": (i32, [vp, MatrixDim, vp, MatrixDim, vp, MatrixDim, vp, i32, f32, f32, f32, vp, i32,
                                           vp, vp, vp, MatrixDim, vp, MatrixDim, vp, i32, vp, MatrixDim, vp, i32, vp]),
     "tnet_affine_grad": (i32, [vp, MatrixDim, vp, MatrixDim, vp, MatrixDim, vp]),
+    "tnet_shared_fwd": (i32, [vp, MatrixDim, vp, MatrixDim, vp, i32, vp, MatrixDim, vp]),
+    "tnet_shared_bwd": (i32, [vp, MatrixDim, vp, MatrixDim, i32, vp, MatrixDim, vp]),
+    "tnet_shared_update": (i32, [vp, MatrixDim, vp, MatrixDim, i32, vp, MatrixDim, vp, i32, vp, vp, f32, f32, f32,
+                                 vp]),
     "tnet_sgd_update": (i32, [vp, vp, vp, i64, f32, f32, f32, vp]),
     "tnet_bias_update": (i32, [vp, MatrixDim, vp, vp, vp, f32, f32, vp, vp]),
     "tnet_softmax_xent": (i32, [vp, MatrixDim, vp, vp, i32, vp, i32, vp, vp]),
@@ -207,6 +211,8 @@ _SIGS = {
     "tnet_rbm_trainer_replay": (i32, [vp, i64]),
     "tnet_net_recurrent_get": (i32, [vp, i32, vp, vp]),
     "tnet_net_recurrent_set": (i32, [vp, i32, vp, vp]),
+    "tnet_net_shared_get": (i32, [vp, i32, vp, vp, vp]),
+    "tnet_net_shared_set": (i32, [vp, i32, vp, vp]),
     "tnet_rnn_trainer_create": (vp, [vp, vp, i32, i32]),
     "tnet_rnn_trainer_free": (i32, [vp]),
     "tnet_rnn_trainer_utterance": (i32, [vp, vp, i32, i32, i32, vp]),

@@ -49,11 +49,23 @@ def _fmt(x: float, prec: int) -> str:
 def write_nnet(layers: Sequence[Layer], path_or_buf, precision: int = 6) -> None:
     """Write layers in the reference text format (default ostream precision = 6 digits)."""
     out = io.StringIO()
+    _write_layers(out, layers, precision)
+    text = out.getvalue()
+    if hasattr(path_or_buf, "write"):
+        path_or_buf.write(text)
+    else:
+        with open(path_or_buf, "w") as f:
+            f.write(text)
+
+
+def _write_layers(out, layers: Sequence[Layer], precision: int) -> None:
     for L in layers:
         out.write(f"{L.tag} {L.n_out} {L.n_in}\n")
-        if L.tag in ("<biasedlinearity>", "<rbm>", "<recurrent>"):
+        if L.tag in ("<biasedlinearity>", "<rbm>", "<recurrent>", "<sharedlinearity>"):
             if L.tag == "<rbm>":
                 out.write(f"{L.extra.get('vis_type', 'bern')} {L.extra.get('hid_type', 'bern')}\n")
+            if L.tag == "<sharedlinearity>":     # cuSharedLinearity.cc:160-176: the instance count first
+                out.write(f"{int(L.extra['n_inst'])}\n")
             Wt = np.asarray(L.W, dtype=np.float32).T   # file holds [n_out x n_in(+n_out)]
             out.write(f"m {Wt.shape[0]} {Wt.shape[1]}\n")
             for row in Wt:
@@ -66,14 +78,15 @@ def write_nnet(layers: Sequence[Layer], path_or_buf, precision: int = 6) -> None
             b = np.asarray(L.b, dtype=np.float32)
             out.write(f"v {b.shape[0]}  " + " ".join(_fmt(v, precision) for v in b) + " ")
             out.write("\n\n")
+        elif L.tag == "<blockarray>":            # cuBlockArray.cc:125-135
+            blocks = L.extra["blocks"]
+            out.write(f" {len(blocks)} ")
+            for k, block in enumerate(blocks):
+                out.write(f"<block> {k + 1}\n")
+                _write_layers(out, block, precision)
+                out.write("<endblock>\n")
         else:
             _write_frontend(out, L, precision)
-    text = out.getvalue()
-    if hasattr(path_or_buf, "write"):
-        path_or_buf.write(text)
-    else:
-        with open(path_or_buf, "w") as f:
-            f.write(text)
 
 
 def _write_frontend(out, L: Layer, precision: int) -> None:
@@ -118,7 +131,6 @@ def read_nnet(path_or_text: str) -> List[Layer]:
         text = path_or_text
     toks = text.split()
     i = 0
-    layers: List[Layer] = []
 
     def read_matrix():
         nonlocal i
@@ -138,38 +150,80 @@ def read_nnet(path_or_text: str) -> List[Layer]:
         i += n
         return v
 
-    while i < len(toks):
-        tag = toks[i].lower()
-        if tag == "<endblock>":
-            break
-        n_out, n_in = int(toks[i + 1]), int(toks[i + 2])
-        i += 3
-        L = Layer(tag, n_out, n_in)
-        if tag == "<biasedlinearity>" or tag == "<recurrent>":
-            L.W = np.ascontiguousarray(read_matrix().T)
-            L.b = read_vector()
-        elif tag == "<rbm>":
-            L.extra["vis_type"] = toks[i].lower()
-            L.extra["hid_type"] = toks[i + 1].lower()
-            i += 2
-            L.W = np.ascontiguousarray(read_matrix().T)
-            L.extra["vis_bias"] = read_vector()
-            L.b = read_vector()
-        elif tag == "<expand>":
-            L.extra["offsets"] = read_vector().astype(np.int64)
-        elif tag == "<copy>":
-            L.extra["indices"] = read_vector().astype(np.int64) - 1
-        elif tag == "<transpose>":
-            L.extra["context"] = int(toks[i])
-            i += 1
-        elif tag == "<blocklinearity>":
-            L.W = np.ascontiguousarray(read_matrix().T)
-        elif tag == "<bias>":
-            L.b = read_vector()
-        elif tag == "<window>":
-            L.extra["window"] = read_vector()
-        layers.append(L)
-    return layers
+    def read_layers() -> List[Layer]:
+        nonlocal i
+        layers: List[Layer] = []
+        while i < len(toks):
+            tag = toks[i].lower()
+            if tag == "<endblock>":
+                i += 1
+                break
+            n_out, n_in = int(toks[i + 1]), int(toks[i + 2])
+            i += 3
+            L = Layer(tag, n_out, n_in)
+            if tag == "<biasedlinearity>" or tag == "<recurrent>":
+                L.W = np.ascontiguousarray(read_matrix().T)
+                L.b = read_vector()
+            elif tag == "<sharedlinearity>":
+                # cuSharedLinearity.cc:99-157 and its three error conditions
+                n = int(toks[i])
+                i += 1
+                if n < 1:
+                    raise ValueError(f"Bad number of instances:{n}")
+                if n_in % n or n_out % n:
+                    raise ValueError("Number of Inputs/Outputs must be divisible by number of instances"
+                                     f" Inputs:{n_in} Outputs{n_out} Intances:{n}")
+                L.extra["n_inst"] = n
+                L.W = np.ascontiguousarray(read_matrix().T)
+                L.b = read_vector()
+                if L.W.shape != (n_in // n, n_out // n) or L.b.shape != (n_out // n,):
+                    raise ValueError("Wrong dimensionalities of matrix/vector in network file")
+            elif tag == "<blockarray>":
+                # cuBlockArray.cc:57-122
+                nb = int(toks[i])
+                i += 1
+                if nb < 1:
+                    raise ValueError(f"Bad number of blocks:{nb}")
+                blocks = []
+                for k in range(nb):
+                    if toks[i].lower() != "<block>":
+                        raise ValueError("<block> keywotd expected")
+                    if int(toks[i + 1]) != k + 1:
+                        raise ValueError(f"Expected block number:{k + 1} read block number: {toks[i + 1]}")
+                    i += 2
+                    block = read_layers()
+                    if not block:
+                        raise ValueError("Cannot read empty network to a block")
+                    blocks.append(block)
+                if sum(b[0].n_in for b in blocks) != n_in:
+                    raise ValueError("Non-matching number of INPUTS!")
+                if sum(b[-1].n_out for b in blocks) != n_out:
+                    raise ValueError("Non-matching number of OUTPUTS!")
+                L.extra["blocks"] = blocks
+            elif tag == "<rbm>":
+                L.extra["vis_type"] = toks[i].lower()
+                L.extra["hid_type"] = toks[i + 1].lower()
+                i += 2
+                L.W = np.ascontiguousarray(read_matrix().T)
+                L.extra["vis_bias"] = read_vector()
+                L.b = read_vector()
+            elif tag == "<expand>":
+                L.extra["offsets"] = read_vector().astype(np.int64)
+            elif tag == "<copy>":
+                L.extra["indices"] = read_vector().astype(np.int64) - 1
+            elif tag == "<transpose>":
+                L.extra["context"] = int(toks[i])
+                i += 1
+            elif tag == "<blocklinearity>":
+                L.W = np.ascontiguousarray(read_matrix().T)
+            elif tag == "<bias>":
+                L.b = read_vector()
+            elif tag == "<window>":
+                L.extra["window"] = read_vector()
+            layers.append(L)
+        return layers
+
+    return read_layers()
 
 
 def gen_mlp_init(dims: Sequence[int], seed: int, gauss: bool = True, negbias: bool = True) -> List[Layer]:
@@ -212,6 +266,22 @@ def gen_rbm_init(n_vis: int, n_hid: int, seed: int, vis_type: str = "gauss", hid
     hb = bias(n_hid, hid_type)
     return [Layer("<rbm>", n_hid, n_vis, np.ascontiguousarray(Wt.T), hb,
                   {"vis_type": vis_type, "hid_type": hid_type, "vis_bias": vb})]
+
+
+def gen_shared_init(n_inst: int, n_in: int, n_out: int, seed: int, gauss: bool = True,
+                    negbias: bool = True) -> List[Layer]:
+    """One <sharedlinearity> of ``n_inst`` instances of an n_in -> n_out transform (the layer is
+    n_inst*n_in -> n_inst*n_out) followed by its <sigmoid>, parameters drawn as gen_mlp_init draws a
+    hidden layer's: W^T ~ 0.1 N(0,1) (--gauss) or U[-0.1, 0.1], bias U[-4.1, -3.9] (--negbias) or 0."""
+    rng = np.random.default_rng(seed)
+    if gauss:
+        Wt = (0.1 * rng.standard_normal((n_out, n_in))).astype(np.float32)
+    else:
+        Wt = (rng.random((n_out, n_in)) / 5.0 - 0.1).astype(np.float32)
+    b = (rng.random(n_out) / 5.0 - 4.1).astype(np.float32) if negbias else np.zeros(n_out, np.float32)
+    return [Layer("<sharedlinearity>", n_inst * n_out, n_inst * n_in, np.ascontiguousarray(Wt.T), b,
+                  {"n_inst": int(n_inst)}),
+            Layer("<sigmoid>", n_inst * n_out, n_inst * n_out)]
 
 
 def gen_recurrent_init(n_in: int, n_hid: int, n_out: int, seed: int, gauss: bool = True,
