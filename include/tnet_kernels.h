@@ -533,6 +533,50 @@ int tnet_shared_update(const float* X, TnetMatrixDim dX, const float* E, TnetMat
                        TnetMatrixDim dW, float* corrW, int ldcorr, float* b, float* corr_b, float scale, float mmt,
                        float l2, void* stream);
 
+/* ---- <discretelinearity> (CuDiscreteLinearity, cuDiscreteLinearity.cc:9-78): block k has its own W_k
+ * [in_k x out_k] between the column stripe X[:, io_k : io_k+in_k] of X [rows x sum in_k] and the stripe
+ * [oo_k, oo_k+out_k) of Y / E [rows x sum out_k] (io_k / oo_k: running sums); one bias [sum out_k].  Each entry
+ * point replaces the reference's per-block OffsetGemm loop (+ AddScaledRow / AddColSum / AddScaled) by one
+ * grouped launch over all blocks (gemm_discrete.hip; one class -- backward, bunch >= 512, a grouped grid of fewer
+ * than 256 workgroups and an out_k of at least 200 per block, aligned E stripes -- instead loops over tnet_sgemm
+ * per block inside tnet_discrete_bwd, which measured faster there: profiles/discrete_linearity.json).  Blocks may
+ * be ragged; any rows / in_k / out_k, stripe origins need no 16-byte alignment (pointers 4-byte aligned, activation
+ * strides multiples of 4 elements).
+ *
+ * The block structure is described once: tnet_discrete_plan_create fixes the packed parameter layout -- all W_k
+ * in one buffer of tnet_discrete_plan_floats floats, W_k row-major at offset w_off_k (a multiple of 4: 16-byte
+ * aligned bases when the buffer is) with row stride ld_k = out_k rounded up to 4 (tnet_discrete_plan_block) --
+ * and uploads the descriptor and tile-prefix tables the kernels search, so a step makes no host -> device copy
+ * and no allocation.  Wp / corrp are buffers in that layout (the stride padding is never written).
+ * TNET_ERR_ARG before any launch: NULL plan / matrix / parameter buffer, n_blocks < 1 or a dimension < 1,
+ * dX.cols != sum in_k, dY.cols / dE.cols != sum out_k, a row-count mismatch, a stride that is no multiple of 4,
+ * a parameter buffer overlapping an activation.
+ *   tnet_discrete_fwd    : Y_k  = X_k W_k + b_k                                  (cuDiscreteLinearity.cc:9-26)
+ *   tnet_discrete_bwd    : Eo_k = E_k W_k^T  (beta 0; every column of Eo written once)          (.cc:29-42)
+ *   tnet_discrete_update : c_k = X_k^T E_k + mmt*corr_k ; corr_k = c_k ; W_k += scale*c_k ; W_k += l2*W_k
+ *                          cb = colsum(E) + mmt*corr_b ; corr_b = cb ; b += scale*cb           (.cc:45-78 with
+ *                          tnet_shared_update's arithmetic; the caller computes scale = -lr/Ndiv, l2 = -lr*wc).
+ *                          `rows` is cut into slices whose partial products are added in a fixed order (no atomics:
+ *                          the same bits every run; bias gradient fp32 inside a 32-row slab, fp64 across slabs),
+ *                          in the per-stream workspace the library keeps.  rows == 0 still applies momentum and
+ *                          weight decay.  corrp / corr_b may be NULL exactly when mmt == 0.
+ * tnet_discrete_loop_routing(0) keeps every call on the grouped launch (tools/discrete_bench.py measures the routed
+ * class both ways); returns the previous setting. */
+typedef struct TnetDiscretePlan TnetDiscretePlan;
+int tnet_discrete_plan_create(const int* n_in, const int* n_out, int n_blocks, TnetDiscretePlan** out);
+int tnet_discrete_plan_free(TnetDiscretePlan* plan);
+long tnet_discrete_plan_floats(const TnetDiscretePlan* plan);
+int tnet_discrete_plan_blocks(const TnetDiscretePlan* plan);
+int tnet_discrete_plan_block(const TnetDiscretePlan* plan, int k, long* w_off, int* ld);
+int tnet_discrete_loop_routing(int enable);
+int tnet_discrete_fwd(const float* X, TnetMatrixDim dX, const float* Wp, const TnetDiscretePlan* plan, const float* b,
+                      float* Y, TnetMatrixDim dY, void* stream);
+int tnet_discrete_bwd(const float* E, TnetMatrixDim dE, const float* Wp, const TnetDiscretePlan* plan, float* Eo,
+                      TnetMatrixDim dEo, void* stream);
+int tnet_discrete_update(const float* X, TnetMatrixDim dX, const float* E, TnetMatrixDim dE,
+                         const TnetDiscretePlan* plan, float* Wp, float* corrp, float* b, float* corr_b, float scale,
+                         float mmt, float l2, void* stream);
+
 /* ---- per-element HybridTaus random numbers (CuRand, curand.tcc / curandkernels.cu) ----------
  * z1..z4: four uint32 state arrays with the element layout of the target matrix (index =
  * col + row*stride), seeded by the caller with lrand48() values > 128 (curand.tcc:36-45) and

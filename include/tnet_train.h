@@ -216,6 +216,15 @@ long tnet_rnn_trainer_frames(TnetRnnTrainer* t);
 int tnet_net_shared_get(TnetNetwork* net, int i, float* W, float* b, int* n_inst);
 int tnet_net_shared_set(TnetNetwork* net, int i, const float* W, const float* b);
 
+/* ---- <discretelinearity> (CuDiscreteLinearity, cuDiscreteLinearity.cc) ---------------------------
+ * tnet_net_discrete_blocks: the block count of component i and the blocks' dimensions (n_in / n_out: arrays of
+ * n_blocks ints; any pointer may be NULL -- ask for the count first).  get / set: block blk's W [in_blk x out_blk]
+ * (host row-major) and the whole layer's bias [n_out]; either may be NULL.  Another component type is an error;
+ * tnet_net_get_params / tnet_net_set_params stay <biasedlinearity>-only. */
+int tnet_net_discrete_blocks(TnetNetwork* net, int i, int* n_blocks, int* n_in, int* n_out);
+int tnet_net_discrete_get(TnetNetwork* net, int i, int blk, float* W, float* b);
+int tnet_net_discrete_set(TnetNetwork* net, int i, int blk, const float* W, const float* b);
+
 /* ---- data parallel (no reference counterpart: Platform.h:143-391 is the CPU analogue) ---- */
 int tnet_comm_unique_id(char out[128]);        /* rank 0 creates, the launcher broadcasts it */
 TnetComm* tnet_comm_create(int rank, int world, const char id[128]);

@@ -8,6 +8,7 @@
 #include "tnet_train.h"
 #include "curbm.h"
 #include "curecurrent.h"
+#include "cudiscrete.h"
 #include "cushared.h"
 #include "htkio.h"
 #include "trainer.h"
@@ -667,6 +668,38 @@ int tnet_net_shared_get(TnetNetwork* h, int i, float* W, float* b, int* n_inst) 
 int tnet_net_shared_set(TnetNetwork* h, int i, const float* W, const float* b) {
   TRY_BEGIN CuSharedLinearity& L = shared_layer(h, i);
   if (W) L.Linearity().CopyFromHost(W, L.Linearity().Rows(), L.Linearity().Cols(), L.Linearity().Cols());
+  if (b) L.Bias().CopyFromHost(b, L.Bias().Dim());
+  CuDevice::Instantiate().Synchronize();
+  TRY_END
+}
+
+// --------------------------------------------------------------------- <discretelinearity>
+static CuDiscreteLinearity& discrete_layer(TnetNetwork* h, int i) {
+  if (i < 0 || i >= h->net.Layers()) Error("component index out of range");
+  auto* p = dynamic_cast<CuDiscreteLinearity*>(&h->net.Layer(i));
+  if (!p) Error("component is not <discretelinearity>");
+  return *p;
+}
+int tnet_net_discrete_blocks(TnetNetwork* h, int i, int* n_blocks, int* n_in, int* n_out) {
+  TRY_BEGIN CuDiscreteLinearity& L = discrete_layer(h, i);
+  if (n_blocks) *n_blocks = L.NBlocks();
+  for (int k = 0; k < L.NBlocks(); ++k) {
+    if (n_in) n_in[k] = (int)L.BlockInputs(k);
+    if (n_out) n_out[k] = (int)L.BlockOutputs(k);
+  }
+  TRY_END
+}
+int tnet_net_discrete_get(TnetNetwork* h, int i, int blk, float* W, float* b) {
+  TRY_BEGIN CuDiscreteLinearity& L = discrete_layer(h, i);
+  if (blk < 0 || blk >= L.NBlocks()) Error("block index out of range");
+  if (W) L.GetBlock(blk, W, L.BlockOutputs(blk));
+  if (b) L.Bias().CopyToHost(b);
+  TRY_END
+}
+int tnet_net_discrete_set(TnetNetwork* h, int i, int blk, const float* W, const float* b) {
+  TRY_BEGIN CuDiscreteLinearity& L = discrete_layer(h, i);
+  if (blk < 0 || blk >= L.NBlocks()) Error("block index out of range");
+  if (W) L.SetBlock(blk, W, L.BlockOutputs(blk));
   if (b) L.Bias().CopyFromHost(b, L.Bias().Dim());
   CuDevice::Instantiate().Synchronize();
   TRY_END

@@ -1,0 +1,153 @@
+// cudiscrete.cpp -- <discretelinearity> on the grouped gfx950 kernels.
+#include "cudiscrete.h"
+
+#include "culayers.h"
+
+namespace TNet {
+
+#define S ((void*)CuDevice::Instantiate().Stream())
+
+CuDiscreteLinearity::~CuDiscreteLinearity() { (void)tnet_discrete_plan_free(mpPlan); }
+
+void CuDiscreteLinearity::PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  CuProfileScope p("CuDiscreteLinearity::Propagate");
+  // Y_k = b_k + X_k W_k for every block (AddScaledRow + one OffsetGemm('N','N') per block,
+  // cuDiscreteLinearity.cc:9-26) in one launch
+  KTScope kt("discrete_fwd:" + std::to_string(mNBlocks) + "x" + std::to_string(GetNInputs()) + "x" +
+                 std::to_string(GetNOutputs()),
+             2.0 * X.Rows() * mMacsPerRow);
+  TNET_SAFE_CALL(tnet_discrete_fwd(X.pCUData(), X.Dim(), mLinearity.pCUData(), mpPlan, mBias.pCUData(), Y.pCUData(),
+                                   Y.Dim(), S));
+}
+
+void CuDiscreteLinearity::BackpropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  CuProfileScope p("CuDiscreteLinearity::Backpropagate");
+  // Y_k = X_k W_k^T with beta 0 (one OffsetGemm('N','T') per block, cuDiscreteLinearity.cc:29-42) in one launch
+  KTScope kt("discrete_bwd:" + std::to_string(mNBlocks) + "x" + std::to_string(GetNInputs()) + "x" +
+                 std::to_string(GetNOutputs()),
+             2.0 * X.Rows() * mMacsPerRow);
+  TNET_SAFE_CALL(tnet_discrete_bwd(X.pCUData(), X.Dim(), mLinearity.pCUData(), mpPlan, Y.pCUData(), Y.Dim(), S));
+}
+
+void CuDiscreteLinearity::UpdateConstants(size_t rows, float* scale, float* l2) const {
+  // cuDiscreteLinearity.cc:50-55, 69-71
+  BaseFloat N = 1;
+  if (mGradDivFrm) N = static_cast<BaseFloat>(rows);
+  BaseFloat mmt_gain = static_cast<BaseFloat>(1.0 / (1.0 - mMomentum));
+  N *= mmt_gain;  // no block-count factor: every block has a gradient of its own
+  *scale = -mLearningRate / N;
+  *l2 = -mLearningRate * mWeightcost;
+}
+
+void CuDiscreteLinearity::Update() {
+  CuProfileScope p("CuDiscreteLinearity::Update");
+  const CuMatrix<BaseFloat>& X = GetInput();
+  const CuMatrix<BaseFloat>& E = GetErrorInput();
+  float scale, l2;
+  UpdateConstants(X.Rows(), &scale, &l2);
+  const bool mmt = mMomentum != 0.0f;
+  // every block's gradient, the bias gradient and the SGD apply in one call; with momentum 0 the correction
+  // buffers are never read, so they are not written either
+  KTScope kt("discrete_upd:" + std::to_string(mNBlocks) + "x" + std::to_string(GetNInputs()) + "x" +
+                 std::to_string(GetNOutputs()),
+             2.0 * X.Rows() * mMacsPerRow);
+  TNET_SAFE_CALL(tnet_discrete_update(X.pCUData(), X.Dim(), E.pCUData(), E.Dim(), mpPlan, mLinearity.pCUData(),
+                                      mmt ? mLinearityCorrection.pCUData() : nullptr, mBias.pCUData(),
+                                      mmt ? mBiasCorrection.pCUData() : nullptr, scale, mMomentum, l2, S));
+}
+
+void CuDiscreteLinearity::GetBlock(int k, BaseFloat* W, size_t ldw) const {
+  long off = 0;
+  int ld = 0;
+  TNET_SAFE_CALL(tnet_discrete_plan_block(mpPlan, k, &off, &ld));
+  TNET_HIP_CALL(hipMemcpy2DAsync(W, ldw * sizeof(BaseFloat), mLinearity.pCUData() + off,
+                                 (size_t)ld * sizeof(BaseFloat), (size_t)mOut[k] * sizeof(BaseFloat), (size_t)mIn[k],
+                                 hipMemcpyDeviceToHost, CuDevice::Instantiate().Stream()));
+  CuDevice::Instantiate().Synchronize();
+}
+
+void CuDiscreteLinearity::SetBlock(int k, const BaseFloat* W, size_t ldw) {
+  long off = 0;
+  int ld = 0;
+  TNET_SAFE_CALL(tnet_discrete_plan_block(mpPlan, k, &off, &ld));
+  TNET_HIP_CALL(hipMemcpy2DAsync(mLinearity.pCUData() + off, (size_t)ld * sizeof(BaseFloat), W,
+                                 ldw * sizeof(BaseFloat), (size_t)mOut[k] * sizeof(BaseFloat),
+                                 (size_t)mIn[k], hipMemcpyHostToDevice, CuDevice::Instantiate().Stream()));
+  CuDevice::Instantiate().Synchronize();
+}
+
+void CuDiscreteLinearity::ReadFromStream(std::istream& rIn) {
+  // block count, then per block the matrix stored transposed as SNet does, then one bias
+  // (cuDiscreteLinearity.cc:81-136)
+  mNBlocks = 0;
+  rIn >> std::ws >> mNBlocks;
+  if (rIn.fail() || mNBlocks < 1) {
+    std::ostringstream os;
+    os << "Bad number of blocks:" << mNBlocks;
+    Error(os.str());
+  }
+  std::vector<BfMatrix> transposes((size_t)mNBlocks);
+  mIn.assign((size_t)mNBlocks, 0);
+  mOut.assign((size_t)mNBlocks, 0);
+  size_t in_dim = 0, out_dim = 0;
+  for (int i = 0; i < mNBlocks; i++) {
+    BfMatrix& transpose = transposes[(size_t)i];
+    ReadMatrixFast(rIn, transpose);
+    if (transpose.Cols() * transpose.Rows() == 0) Error("Missing linearity matrix in network file");
+    mIn[(size_t)i] = (int)transpose.Cols();
+    mOut[(size_t)i] = (int)transpose.Rows();
+    in_dim += transpose.Cols();
+    out_dim += transpose.Rows();
+  }
+  BfVector bias;
+  ReadVectorFast(rIn, bias);
+  if (bias.Dim() == 0) Error("Missing bias vector in network file");
+  if (out_dim != GetNOutputs() || in_dim != GetNInputs() || bias.Dim() != GetNOutputs()) {
+    std::ostringstream os;
+    os << "Wrong dimensionalities of matrix/vector in network file\n"
+       << "Inputs:" << GetNInputs() << "Outputs:" << GetNOutputs() << "\n"
+       << "linearityCols:" << in_dim << "linearityRows:" << out_dim << "biasDims:" << bias.Dim() << "\n";
+    Error(os.str());
+  }
+  // the packed layout and the kernels' device tables, once (on the device the library has selected)
+  CuDevice::Instantiate();
+  (void)tnet_discrete_plan_free(mpPlan);
+  mpPlan = nullptr;
+  TNET_SAFE_CALL(tnet_discrete_plan_create(mIn.data(), mOut.data(), mNBlocks, &mpPlan));
+  const size_t total = (size_t)tnet_discrete_plan_floats(mpPlan);
+  std::vector<BaseFloat> packed(total, 0.0f);
+  mMacsPerRow = 0.0;
+  for (int i = 0; i < mNBlocks; i++) {
+    long off = 0;
+    int ld = 0;
+    TNET_SAFE_CALL(tnet_discrete_plan_block(mpPlan, i, &off, &ld));
+    const BfMatrix& t = transposes[(size_t)i];
+    for (size_t r = 0; r < t.Cols(); r++)
+      for (size_t c = 0; c < t.Rows(); c++) packed[(size_t)off + r * (size_t)ld + c] = t(c, r);
+    mMacsPerRow += (double)t.Cols() * (double)t.Rows();
+  }
+  mLinearity.CopyFromHost(packed.data(), total);
+  mBias.CopyFrom(bias);
+  // correction buffers start at zero
+  mLinearityCorrection.Init(total);
+  mLinearityCorrection.SetZero();
+  mBiasCorrection.Init(mBias.Dim());
+  mBiasCorrection.SetZero();
+}
+
+void CuDiscreteLinearity::WriteToStream(std::ostream& rOut) {
+  // cuDiscreteLinearity.cc:139-156
+  rOut << mNBlocks << "\n";
+  for (int i = 0; i < mNBlocks; i++) {
+    BfMatrix tmp((size_t)mIn[(size_t)i], (size_t)mOut[(size_t)i]);
+    GetBlock(i, tmp.pData(), tmp.Stride());
+    BfMatrix transpose(tmp, TRANS);
+    rOut << transpose;
+  }
+  BfVector vec;
+  mBias.CopyTo(vec);
+  rOut << vec;
+  rOut << std::endl;
+}
+
+}  // namespace TNet

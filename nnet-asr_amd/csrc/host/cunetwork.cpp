@@ -4,6 +4,7 @@
 #include "cufeat.h"
 #include "curbm.h"
 #include "curecurrent.h"
+#include "cudiscrete.h"
 #include "cushared.h"
 
 #include <algorithm>
@@ -163,6 +164,8 @@ CuComponent* CuNetwork::ComponentFactory(std::istream& rIn) {
   // convolutive-bottleneck / universal-context layers (cuNetwork.cc:286, 303)
   else if (tag == "<sharedlinearity>") pRet = new CuSharedLinearity(nInputs, nOutputs, pPred);
   else if (tag == "<blockarray>") pRet = new CuBlockArray(nInputs, nOutputs, pPred);
+  // block-diagonal layer of band-split / hierarchical bottleneck networks (cuNetwork.cc:253, 285)
+  else if (tag == "<discretelinearity>") pRet = new CuDiscreteLinearity(nInputs, nOutputs, pPred);
   // feature front end (cuNetwork.cc:263-268, cuCRBEDctFeat.h)
   else if (tag == "<expand>") pRet = new CuExpand(nInputs, nOutputs, pPred);
   else if (tag == "<copy>") pRet = new CuCopy(nInputs, nOutputs, pPred);

@@ -1,0 +1,412 @@
+// gemm_discrete.hip -- grouped (ragged) GEMMs of <discretelinearity> (src/CuTNetLib/cuDiscreteLinearity.cc:9-78).
+//
+// Block k of the layer maps its own column stripe of the input (in_k wide, origin io_k = sum_{j<k} in_j) to its
+// own stripe of the output (out_k wide, origin oo_k) through a weight matrix W_k [in_k x out_k] of its own; one
+// bias covers the whole output.  The reference loops over OffsetGemm, one call per block and direction; here
+// each direction is one launch over ALL blocks:
+//   tnet_discrete_fwd    Y[:, oo_k : oo_k+out_k] = X[:, io_k : io_k+in_k] W_k + b[oo_k : oo_k+out_k]
+//   tnet_discrete_bwd    Eo[:, io_k : io_k+in_k] = E[:, oo_k : oo_k+out_k] W_k^T            (beta 0)
+//   tnet_discrete_update G_k = X_k^T E_k, colsum(E) and the SGD apply: the depth `rows` is cut into row-chunk
+//                        slices whose partial products go to the per-stream workspace in the layout of the packed
+//                        parameters; a second launch over the packed buffer adds them in slice order (no atomics:
+//                        same bits every run) and applies gemm_shared.hip's combine arithmetic to every W_k and b.
+//
+// The block structure is fixed when the layer is read, so it is described once (TnetDiscretePlan): the packed
+// parameter layout (every W_k in one buffer, base 16-byte aligned, row stride a multiple of 4), a device table
+// of block descriptors and, per direction and tile size, the prefix sums of the blocks' tile counts.  The grid
+// is flat; a workgroup finds its block by a binary search of the prefix array from blockIdx alone (uniform over
+// the workgroup, so window pointers and extents stay scalar), one block's tiles are consecutive, and the block
+// count is unbounded (the tables live in device memory, not in the kernel arguments).  The tile core is
+// gemm_tile.h's, shared with gemm_shared.hip.  A stripe is read with 16-byte loads where its origin allows it
+// (descriptor flag) and through the masked scalar path otherwise (in_k = 39 puts later origins off 16 bytes).
+//
+// (One shape class -- backward, few blocks with a deep K at a large bunch, where the grouped launch has fewer
+// workgroups than the GPU has CUs -- runs as a per-block loop over the library's tuned GEMM inside
+// tnet_discrete_bwd: loop_class below.)
+#include "gemm_tile.h"
+
+#include <algorithm>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+struct DiscDesc {
+  int io, oo, in, out;  // stripe origins and widths
+  long w_off;           // W_k's first element in the packed buffer (a multiple of 4)
+  int ld;               // W_k's row stride (a multiple of 4)
+  int flags;            // 16-byte loads allowed: bit 0 the input stripe (io % 4 == 0), bit 1 the output stripe
+};
+
+// direction of a tile-prefix array: what a block's tiles cover
+enum { DIR_OUT = 0, DIR_IN = 1, DIR_W = 2 };  // fwd: out_k columns; bwd: in_k columns; update: in_k x out_k
+
+struct TnetDiscretePlan {
+  int nb = 0, sum_in = 0, sum_out = 0;
+  long total = 0;               // floats of the packed parameter buffer
+  int max_out = 0;              // the deepest K of the backward pass
+  bool out_aligned = false;     // every output stripe origin a multiple of 4
+  bool padded_in = false;       // some input stripe origin is not: the backward loop stages Eo (below)
+  int pad_cols = 0;             // columns of the staged Eo: every stripe padded to a multiple of 4
+  std::vector<DiscDesc> desc;   // host copy
+  std::vector<int> pre;         // host copy of the prefix arrays: [dir][tile size 64 | 128][nb + 1]
+  void* dev = nullptr;          // one device allocation: descriptors, w_off[nb + 1], prefix arrays, from_pad
+  const DiscDesc* d_desc = nullptr;
+  const long* d_woff = nullptr;
+  const int* d_pre = nullptr;
+  const int* d_from_pad = nullptr;  // [sum_in]: column of the staged Eo that holds column j of Eo
+  const int* prefix(int dir, int T) const { return pre.data() + (size_t)(dir * 2 + (T == 4)) * (nb + 1); }
+  const int* d_prefix(int dir, int T) const { return d_pre + (size_t)(dir * 2 + (T == 4)) * (nb + 1); }
+};
+
+namespace tnetk {
+namespace {
+
+struct DiscP {
+  const DiscDesc* desc;
+  const int* pre;              // this launch's prefix array [nb + 1]
+  int nb;
+  const float* A; long lda;    // fwd: X; bwd: E; update: X
+  const float* E; long lde;    // update: E
+  const float* Wp;
+  float* C; long ldc;          // fwd: Y; bwd: Eo
+  const float* bias;
+  int rows, mult;              // mult: fwd / bwd tile rows, update K slices; a block has mult * (prefix share) tiles
+  int a16, e16, w16;           // the operands' base pointers are 16-byte aligned
+  int kchunk;                  // update: rows per K slice (a multiple of kSlab)
+  float* part; long total;     // partial products [kslices][total], packed like the parameters
+  double* bpart; long ldbp;    // partial column sums of E [kslices][sum_out]
+};
+
+template <int MODE, int T>
+__global__ __launch_bounds__(kThreads) void discrete_gemm_kernel(const DiscP p) {
+  constexpr int BT = 32 * T;
+  // blockIdx -> block: the last k with pre[k] * mult <= blockIdx (pre is strictly increasing: every block has a tile)
+  const long q = (long)blockIdx.x;
+  int lo = 0, hi = p.nb;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if ((long)p.pre[mid] * p.mult <= q) lo = mid;
+    else hi = mid;
+  }
+  const DiscDesc d = p.desc[lo];
+  const int share = p.pre[lo + 1] - p.pre[lo];
+  const int rem = (int)(q - (long)p.pre[lo] * p.mult);
+  const float* Wk = p.Wp + d.w_off;
+  TileWork w;
+  if (MODE == MODE_UPD) {
+    // rem -> (slice, tile-row, tile-col): `share` = tile rows x tile cols of W_k
+    const int slice = rem / share, t = rem % share, tn = (d.out + BT - 1) / BT;
+    const long krow0 = (long)slice * p.kchunk;
+    w.A = p.A + d.io + krow0 * p.lda; w.lda = p.lda;  // A[m][k] = X[k][io + m]: m contiguous
+    w.B = p.E + d.oo + krow0 * p.lde; w.ldb = p.lde;
+    w.M = d.in; w.N = d.out; w.K = min(p.kchunk, p.rows - (int)krow0);
+    w.bm = (t / tn) * BT; w.bn = (t % tn) * BT;
+    w.vecA = p.a16 & d.flags; w.vecB = p.e16 & (d.flags >> 1);
+    w.C = nullptr; w.ldc = 0; w.bias = nullptr;
+    w.P = p.part + (long)slice * p.total + d.w_off; w.ldp = d.ld;
+    w.bp = p.bpart + (long)slice * p.ldbp + d.oo;
+  } else {
+    // rem -> (tile-row, tile-col): `share` = tile columns of this block's output stripe
+    const int n = MODE == MODE_FWD ? d.out : d.in, k = MODE == MODE_FWD ? d.in : d.out;
+    const int ao = MODE == MODE_FWD ? d.io : d.oo, co = MODE == MODE_FWD ? d.oo : d.io;
+    w.A = p.A + ao; w.lda = p.lda;
+    w.B = Wk; w.ldb = d.ld;  // fwd: B[k][n] = W_k[k][n]; bwd: B[k][n] = W_k[n][k], k contiguous
+    w.M = p.rows; w.N = n; w.K = k;
+    w.bm = (rem / share) * BT; w.bn = (rem % share) * BT;
+    w.vecA = p.a16 & (MODE == MODE_FWD ? d.flags : d.flags >> 1); w.vecB = p.w16;
+    w.C = p.C + co; w.ldc = p.ldc;
+    w.bias = MODE == MODE_FWD ? p.bias + d.oo : nullptr;
+    w.P = nullptr; w.ldp = 0; w.bp = nullptr;
+  }
+  tile_gemm<MODE, T, 2>(w);  // two k-tiles of loads in flight: ragged layers launch few workgroups with deep K
+}
+
+// The update's second launch, over the packed buffer.  Element idx belongs to the last block whose w_off <= idx
+// (binary search); inside W_k's rows the stride padding [out_k, ld_k) is left alone.  The slices' partial products
+// are added in slice order, then corr = g + mmt*corr ; W += scale*corr ; W += l2*W.  The last sum_out threads:
+// the bias, its gradient the slices' column sums added in fp64 in the same order, corr_b = g + mmt*corr_b ;
+// b += scale*corr_b (no weight decay on the bias, cuDiscreteLinearity.cc:74-77).
+__global__ __launch_bounds__(kThreads) void discrete_combine_kernel(const DiscDesc* __restrict__ desc,
+                                                                    const long* __restrict__ woff, int nb, long total,
+                                                                    const float* __restrict__ P,
+                                                                    const double* __restrict__ bpart, int sum_out,
+                                                                    int Z, float* __restrict__ Wp,
+                                                                    float* __restrict__ corrp, float* __restrict__ b,
+                                                                    float* __restrict__ corr_b, float scale, float mmt,
+                                                                    float l2) {
+  const long idx = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (idx < total) {
+    int lo = 0, hi = nb;
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (woff[mid] <= idx) lo = mid;
+      else hi = mid;
+    }
+    const int col = (int)((idx - woff[lo]) % desc[lo].ld);
+    if (col >= desc[lo].out) return;
+    float g = P[idx];
+    for (int z = 1; z < Z; ++z) g += P[(long)z * total + idx];
+    float c = g;
+    if (corrp) {
+      c = g + mmt * corrp[idx];
+      corrp[idx] = c;
+    }
+    float w = Wp[idx];
+    w = w + scale * c;
+    w = w + l2 * w;
+    Wp[idx] = w;
+  } else if (idx < total + sum_out) {
+    const int col = (int)(idx - total);
+    double s = 0.0;
+    for (int z = 0; z < Z; ++z) s += bpart[(long)z * sum_out + col];
+    float g = (float)s;
+    if (corr_b) {
+      g = g + mmt * corr_b[col];
+      corr_b[col] = g;
+    }
+    b[col] = b[col] + scale * g;
+  }
+}
+
+// 128x128 tiles where they still give every CU a workgroup (gemm_shared.hip's rule) AND the blocks fill them: a
+// ragged layer of narrow blocks has as many 128-tiles as 64-tiles, each mostly empty, so the 64-tile count has to
+// be at least three times the 128-tile count (four times for blocks that are multiples of 128)
+int pick_tile(const TnetDiscretePlan& pl, int dir, int rows) {
+  const long big = (long)pl.prefix(dir, 4)[pl.nb] * (dir == DIR_W ? 1 : cdiv(rows, 128));
+  const long small = (long)pl.prefix(dir, 2)[pl.nb] * (dir == DIR_W ? 1 : cdiv(rows, 64));
+  return big >= 200 && small >= 3 * big ? 4 : 2;
+}
+
+// Shape class routed to the per-block loop (measured, tools/discrete_bench.py / profiles/discrete_linearity.json):
+// backward of the ragged (39, 120, 281) -> (64, 256, 704) layer.  Its grouped launch is 8 tile columns wide, fewer
+// workgroups than CUs up to bunch 2047, so its time is that of the workgroups that run the 704-deep K alone
+// (28.6 us at bunch 256, 28.9 at 1024), while three tuned GEMMs and a scatter take 25.5 us at bunch 1024
+// (0.88x) and 29.8 us at 256 (1.04x).  The class: the 64-tile grid below one workgroup per CU (256), the bunch at
+// least 512 (between the two measured sizes), and the deepest K at least 200 per block (a k-tile of the lone
+// workgroup costs ~0.04 us per k, a GEMM launch of the loop ~8 us per block: 4 x (512 -> 512) and the 23-block
+// layer stay grouped, where they measured 1.05x - 21x).  tnet_sgemm needs 16-byte aligned operands: the E stripes
+// must be (out_aligned); where an Eo stripe is not, the GEMMs write a copy of Eo with every stripe padded to 4
+// columns, in the kept per-stream workspace, and one tnetF_rearrange scatters it -- what the measured loop did.
+constexpr int kCUs = 256, kLoopMinRows = 512, kLoopKPerBlock = 200;
+bool g_loop_routing = true;
+bool loop_class(const TnetDiscretePlan& pl, int rows, const void* e, const void* w, const void* eo) {
+  return g_loop_routing && pl.out_aligned && rows >= kLoopMinRows &&
+         (long)pl.prefix(DIR_IN, 2)[pl.nb] * cdiv(rows, 64) < kCUs && pl.max_out >= (long)kLoopKPerBlock * pl.nb &&
+         aligned16(e) && aligned16(w) && (pl.padded_in || aligned16(eo));
+}
+
+template <int MODE>
+int launch_tiles(DiscP& p, const TnetDiscretePlan& pl, int dir, int T, hipStream_t st) {
+  p.desc = pl.d_desc;
+  p.pre = pl.d_prefix(dir, T);
+  p.nb = pl.nb;
+  const long grid = (long)pl.prefix(dir, T)[pl.nb] * p.mult;
+  if (grid <= 0 || grid > 0x7fffffffL) return TNET_ERR_ARG;
+  if (T == 4) discrete_gemm_kernel<MODE, 4><<<(unsigned)grid, kThreads, 0, st>>>(p);
+  else discrete_gemm_kernel<MODE, 2><<<(unsigned)grid, kThreads, 0, st>>>(p);
+  TNET_LAUNCH_CHECK();
+  return TNET_OK;
+}
+
+bool vec_arg_ok(const void* q, long n) { return q && aligned4(q) && n > 0; }
+bool overlaps_params(const void* q, long n, const void* a, TnetMatrixDim da) {
+  return da.rows > 0 && overlap_bytes(q, (size_t)n * 4, a, (size_t)da.rows * (size_t)da.stride * 4);
+}
+
+}  // namespace
+}  // namespace tnetk
+
+using namespace tnetk;
+
+extern "C" int tnet_discrete_plan_create(const int* n_in, const int* n_out, int n_blocks, TnetDiscretePlan** out) {
+  if (!n_in || !n_out || n_blocks < 1 || !out) return TNET_ERR_ARG;
+  std::unique_ptr<TnetDiscretePlan> pl(new TnetDiscretePlan);
+  pl->nb = n_blocks;
+  pl->desc.resize(n_blocks);
+  pl->pre.assign((size_t)6 * (n_blocks + 1), 0);
+  std::vector<long> woff(n_blocks + 1, 0);
+  long io = 0, oo = 0, total = 0, pio = 0;
+  std::vector<int> from_pad;
+  pl->out_aligned = true;
+  long tiles[6] = {0, 0, 0, 0, 0, 0};
+  for (int k = 0; k < n_blocks; ++k) {
+    if (n_in[k] < 1 || n_out[k] < 1) return TNET_ERR_ARG;
+    DiscDesc& d = pl->desc[k];
+    d.io = (int)io; d.oo = (int)oo; d.in = n_in[k]; d.out = n_out[k];
+    d.ld = (n_out[k] + 3) & ~3;
+    d.w_off = total;  // in_k * ld_k is a multiple of 4, so every base stays 16-byte aligned
+    d.flags = ((io & 3) == 0 ? 1 : 0) | ((oo & 3) == 0 ? 2 : 0);
+    woff[k] = total;
+    pl->max_out = std::max(pl->max_out, n_out[k]);
+    pl->out_aligned = pl->out_aligned && (oo & 3) == 0;
+    pl->padded_in = pl->padded_in || (io & 3) != 0;
+    for (int j = 0; j < n_in[k]; ++j) from_pad.push_back((int)(pio + j));
+    pio += (n_in[k] + 3) & ~3;
+    for (int t = 0; t < 2; ++t) {
+      const int bt = t ? 128 : 64;
+      const long add[3] = {cdiv(n_out[k], bt), cdiv(n_in[k], bt), (long)cdiv(n_in[k], bt) * cdiv(n_out[k], bt)};
+      for (int dir = 0; dir < 3; ++dir) {
+        tiles[dir * 2 + t] += add[dir];
+        if (tiles[dir * 2 + t] > 0x7fffffffL) return TNET_ERR_ARG;
+        pl->pre[(size_t)(dir * 2 + t) * (n_blocks + 1) + k + 1] = (int)tiles[dir * 2 + t];
+      }
+    }
+    io += n_in[k];
+    oo += n_out[k];
+    total += (long)n_in[k] * d.ld;
+    if (io > 0x7fffffffL || oo > 0x7fffffffL || pio > 0x7fffffffL) return TNET_ERR_ARG;
+  }
+  woff[n_blocks] = total;
+  pl->sum_in = (int)io; pl->sum_out = (int)oo; pl->total = total; pl->pad_cols = (int)pio;
+  // one upload, at load time: no host -> device copy and no allocation in a steady-state step
+  const size_t b_desc = ((size_t)n_blocks * sizeof(DiscDesc) + 15) & ~(size_t)15;
+  const size_t b_woff = ((size_t)(n_blocks + 1) * sizeof(long) + 15) & ~(size_t)15;
+  const size_t b_pre = pl->pre.size() * sizeof(int);
+  const size_t b_pad = from_pad.size() * sizeof(int);
+  std::vector<char> host(b_desc + b_woff + b_pre + b_pad, 0);
+  std::memcpy(host.data(), pl->desc.data(), (size_t)n_blocks * sizeof(DiscDesc));
+  std::memcpy(host.data() + b_desc, woff.data(), (size_t)(n_blocks + 1) * sizeof(long));
+  std::memcpy(host.data() + b_desc + b_woff, pl->pre.data(), b_pre);
+  std::memcpy(host.data() + b_desc + b_woff + b_pre, from_pad.data(), b_pad);
+  if (hipMalloc(&pl->dev, host.size()) != hipSuccess) return TNET_ERR_RUNTIME;
+  if (hipMemcpy(pl->dev, host.data(), host.size(), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(pl->dev);
+    return TNET_ERR_RUNTIME;
+  }
+  pl->d_desc = (const DiscDesc*)pl->dev;
+  pl->d_woff = (const long*)((char*)pl->dev + b_desc);
+  pl->d_pre = (const int*)((char*)pl->dev + b_desc + b_woff);
+  pl->d_from_pad = (const int*)((char*)pl->dev + b_desc + b_woff + b_pre);
+  *out = pl.release();
+  return TNET_OK;
+}
+
+extern "C" int tnet_discrete_plan_free(TnetDiscretePlan* plan) {
+  if (!plan) return TNET_OK;
+  if (plan->dev && hipFree(plan->dev) != hipSuccess) return TNET_ERR_RUNTIME;
+  delete plan;
+  return TNET_OK;
+}
+
+extern "C" long tnet_discrete_plan_floats(const TnetDiscretePlan* plan) { return plan ? plan->total : -1; }
+extern "C" int tnet_discrete_plan_blocks(const TnetDiscretePlan* plan) { return plan ? plan->nb : -1; }
+extern "C" int tnet_discrete_plan_block(const TnetDiscretePlan* plan, int k, long* w_off, int* ld) {
+  if (!plan || k < 0 || k >= plan->nb) return TNET_ERR_ARG;
+  if (w_off) *w_off = plan->desc[k].w_off;
+  if (ld) *ld = plan->desc[k].ld;
+  return TNET_OK;
+}
+extern "C" int tnet_discrete_loop_routing(int enable) {
+  const int was = g_loop_routing;
+  g_loop_routing = enable != 0;
+  return was;
+}
+
+extern "C" int tnet_discrete_fwd(const float* X, TnetMatrixDim dX, const float* Wp, const TnetDiscretePlan* plan,
+                                 const float* b, float* Y, TnetMatrixDim dY, void* stream) {
+  if (!plan || !dim_ok(X, dX) || !dim_ok(Y, dY) || !vec_arg_ok(Wp, plan->total) || !vec_arg_ok(b, plan->sum_out) ||
+      dX.cols != plan->sum_in || dY.cols != plan->sum_out || dY.rows != dX.rows)
+    return TNET_ERR_ARG;
+  if (overlaps_params(Wp, plan->total, X, dX) || overlaps_params(Wp, plan->total, Y, dY) ||
+      overlaps_params(b, plan->sum_out, Y, dY) || overlap(X, dX, Y, dY))
+    return TNET_ERR_ARG;
+  if (dX.rows == 0) return TNET_OK;
+  DiscP p{};
+  p.A = X; p.lda = dX.stride;
+  p.Wp = Wp;
+  p.C = Y; p.ldc = dY.stride;
+  p.bias = b;
+  p.rows = dX.rows;
+  p.a16 = aligned16(X); p.w16 = aligned16(Wp);
+  const int T = pick_tile(*plan, DIR_OUT, dX.rows);
+  p.mult = cdiv(dX.rows, 32 * T);
+  return launch_tiles<MODE_FWD>(p, *plan, DIR_OUT, T, (hipStream_t)stream);
+}
+
+extern "C" int tnet_discrete_bwd(const float* E, TnetMatrixDim dE, const float* Wp, const TnetDiscretePlan* plan,
+                                 float* Eo, TnetMatrixDim dEo, void* stream) {
+  if (!plan || !dim_ok(E, dE) || !dim_ok(Eo, dEo) || !vec_arg_ok(Wp, plan->total) || dE.cols != plan->sum_out ||
+      dEo.cols != plan->sum_in || dEo.rows != dE.rows)
+    return TNET_ERR_ARG;
+  if (overlaps_params(Wp, plan->total, E, dE) || overlaps_params(Wp, plan->total, Eo, dEo) || overlap(E, dE, Eo, dEo))
+    return TNET_ERR_ARG;
+  if (dE.rows == 0) return TNET_OK;
+  if (loop_class(*plan, dE.rows, E, Wp, Eo)) {
+    float* dst = Eo;
+    int ldd = dEo.stride;
+    if (plan->padded_in) {  // staged: stripe k at column sum_{j<k} round4(in_j), rows 256 bytes apart
+      ldd = (plan->pad_cols + 63) & ~63;
+      dst = (float*)tile_workspace((size_t)dE.rows * ldd * sizeof(float), (hipStream_t)stream);
+      if (!dst) return TNET_ERR_RUNTIME;
+    }
+    long po = 0;
+    for (const DiscDesc& d : plan->desc) {
+      const int rc = tnet_sgemm('N', 'T', dE.rows, d.in, d.out, 1.f, E + d.oo, dE.stride, Wp + d.w_off, d.ld, 0.f,
+                                dst + (plan->padded_in ? po : (long)d.io), ldd, stream);
+      if (rc) return rc;
+      po += (d.in + 3) & ~3;
+    }
+    if (plan->padded_in)
+      return tnetF_rearrange(Eo, dst, plan->d_from_pad, dEo, TnetMatrixDim{dE.rows, plan->pad_cols, ldd}, stream);
+    return TNET_OK;
+  }
+  DiscP p{};
+  p.A = E; p.lda = dE.stride;
+  p.Wp = Wp;
+  p.C = Eo; p.ldc = dEo.stride;
+  p.rows = dE.rows;
+  p.a16 = aligned16(E); p.w16 = aligned16(Wp);
+  const int T = pick_tile(*plan, DIR_IN, dE.rows);
+  p.mult = cdiv(dE.rows, 32 * T);
+  return launch_tiles<MODE_BWD>(p, *plan, DIR_IN, T, (hipStream_t)stream);
+}
+
+extern "C" int tnet_discrete_update(const float* X, TnetMatrixDim dX, const float* E, TnetMatrixDim dE,
+                                    const TnetDiscretePlan* plan, float* Wp, float* corrp, float* b, float* corr_b,
+                                    float scale, float mmt, float l2, void* stream) {
+  if (!plan || !dim_ok(X, dX) || !dim_ok(E, dE) || !vec_arg_ok(Wp, plan->total) || !vec_arg_ok(b, plan->sum_out) ||
+      dX.cols != plan->sum_in || dE.cols != plan->sum_out || dE.rows != dX.rows)
+    return TNET_ERR_ARG;
+  if ((corrp && !aligned4(corrp)) || (corr_b && !aligned4(corr_b))) return TNET_ERR_ARG;
+  if ((!corrp || !corr_b) && mmt != 0.f) return TNET_ERR_ARG;  // nullable only where they are never read
+  const long nw = plan->total, nb = plan->sum_out;
+  const size_t bw = (size_t)nw * 4, bb = (size_t)nb * 4;
+  // no parameter buffer on an activation, no two parameter buffers on each other
+  for (const void* q : {(const void*)Wp, (const void*)corrp})
+    if (overlaps_params(q, nw, X, dX) || overlaps_params(q, nw, E, dE) || overlap_bytes(q, bw, b, bb) ||
+        overlap_bytes(q, bw, corr_b, bb))
+      return TNET_ERR_ARG;
+  for (const void* q : {(const void*)b, (const void*)corr_b})
+    if (overlaps_params(q, nb, X, dX) || overlaps_params(q, nb, E, dE)) return TNET_ERR_ARG;
+  if (overlap_bytes(Wp, bw, corrp, bw) || overlap_bytes(b, bb, corr_b, bb)) return TNET_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = dX.rows;
+  DiscP p{};
+  p.A = X; p.lda = dX.stride;
+  p.E = E; p.lde = dE.stride;
+  p.rows = rows;
+  p.a16 = aligned16(X); p.e16 = aligned16(E);
+  // K slices: rows cut (in multiples of the 32-row slab) until about two workgroups per CU are in flight
+  // (tnet_shared_update's rule; every block has the same depth, so one cut serves all)
+  const int T = rows > 0 ? pick_tile(*plan, DIR_W, rows) : 2;
+  const long tiles = plan->prefix(DIR_W, T)[plan->nb];
+  int want = (int)std::min<long>(cdiv(512, tiles), 64);
+  want = std::max(1, std::min(want, cdiv(std::max(rows, 1), kSlab)));
+  p.kchunk = cdiv(cdiv(std::max(rows, 1), want), kSlab) * kSlab;
+  p.mult = cdiv(std::max(rows, 1), p.kchunk);
+  p.total = nw;
+  p.ldbp = nb;
+  const size_t bbytes = (((size_t)p.mult * nb * sizeof(double)) + 255) & ~(size_t)255;
+  char* ws = (char*)tile_workspace(bbytes + (size_t)p.mult * nw * sizeof(float), st);
+  if (!ws) return TNET_ERR_RUNTIME;
+  p.bpart = (double*)ws;
+  p.part = (float*)(ws + bbytes);
+  // rows == 0: K = 0, every slice stores zeros (the SGD still applies momentum and weight decay)
+  const int rc = launch_tiles<MODE_UPD>(p, *plan, DIR_W, T, st);
+  if (rc) return rc;
+  discrete_combine_kernel<<<(unsigned)cdiv(nw + nb, kThreads), kThreads, 0, st>>>(
+      plan->d_desc, plan->d_woff, plan->nb, nw, p.part, p.bpart, (int)nb, p.mult, Wp, corrp, b, corr_b, scale, mmt,
+      l2);
+  TNET_LAUNCH_CHECK();
+  return TNET_OK;
+}

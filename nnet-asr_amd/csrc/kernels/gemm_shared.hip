@@ -13,26 +13,20 @@
 // (One shape class -- a single instance's product already filling the GPU, at aligned windows -- runs forward and
 // backward as a per-window loop over the library's tuned GEMM inside the entry points: loop_class below.)
 //
-// All three run one tile kernel on v_mfma_f32_16x16x4_f32 (fp32 in / fp32 accumulate): 256 threads = 2 x 2
-// waves, a 64x64 or 128x128 output tile, k-tiles of 16 staged through a double-buffered LDS image
-// [k][m or n] (row pitch tile + 16 floats: the four k rows a wave's MFMA operand read touches fall on disjoint
-// banks), the next k-tile's global loads in flight while the current one is multiplied.  An operand is read
-// with 16-byte loads when its pointer, window origins and stride allow it and through a masked scalar path
-// otherwise (in = 39 puts every window origin off 16 bytes); rows, in and out need no tile multiple:
+// All three run the tile core of gemm_tile.h (shared with gemm_discrete.hip) on v_mfma_f32_16x16x4_f32 (fp32 in /
+// fp32 accumulate): 256 threads = 2 x 2 waves, a 64x64 or 128x128 output tile, k-tiles of 16 staged through a
+// double-buffered LDS image [k][m or n] (row pitch tile + 16 floats: the four k rows a wave's MFMA operand read
+// touches fall on disjoint banks), the next k-tile's global loads in flight while the current one is multiplied.
+// An operand is read with 16-byte loads when its pointer, window origins and stride allow it and through a masked
+// scalar path otherwise (in = 39 puts every window origin off 16 bytes); rows, in and out need no tile multiple:
 // out-of-range elements are never read (they enter the product as zeros) and never stored.
-#include "kcommon.h"
+#include "gemm_tile.h"
 
 #include <map>
 #include <mutex>
 
 namespace tnetk {
 namespace {
-
-constexpr int kBK = 16;       // k-tile depth
-constexpr int kThreads = 256; // 2 x 2 waves
-constexpr int kSlab = 32;     // rows whose column sum stays in fp32 (the project's slab size)
-
-enum { MODE_FWD = 0, MODE_BWD = 1, MODE_UPD = 2 };
 
 struct SharedP {
   const float* A; long lda; int a_step;  // A operand: base, row stride, per-instance column origin step
@@ -48,85 +42,14 @@ struct SharedP {
   double* bpart; long ldbp;              // partial column sums of E [n_inst * kslices][ldbp]
 };
 
-// One thread's share of a [BMN x 16] operand tile: BMN / 64 groups of four elements.
-//   KC (k contiguous in memory: elem(mn, k) = base[mn * ld + k]): the four are consecutive k of one row
-//   MC (mn contiguous:          elem(mn, k) = base[k * ld + mn]): the four are consecutive mn of one k row
-template <int BMN, bool KC>
-__device__ __forceinline__ void tile_coord(int r, int& mn, int& k) {
-  const int e = (int)threadIdx.x + kThreads * r;
-  if (KC) {
-    mn = e >> 2;
-    k = (e & 3) * 4;
-  } else {
-    k = e / (BMN / 4);
-    mn = (e % (BMN / 4)) * 4;
-  }
-}
-
-template <int BMN, bool KC>
-__device__ __forceinline__ void load_tile(const float* __restrict__ base, long ld, int mn0, int MN, int k0, int K,
-                                          int vec, f32x4 (&v)[BMN / 64]) {
-#pragma unroll
-  for (int r = 0; r < BMN / 64; ++r) {
-    int mn, k;
-    tile_coord<BMN, KC>(r, mn, k);
-    const int gmn = mn0 + mn, gk = k0 + k;
-    f32x4 x = {0.f, 0.f, 0.f, 0.f};
-    if (KC) {
-      if (gmn < MN && gk < K) {
-        const float* q = base + (long)gmn * ld + gk;
-        if (vec && gk + 3 < K) {
-          x = *(const f32x4*)q;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (gk + j < K) x[j] = q[j];
-        }
-      }
-    } else {
-      if (gk < K && gmn < MN) {
-        const float* q = base + (long)gk * ld + gmn;
-        if (vec && gmn + 3 < MN) {
-          x = *(const f32x4*)q;
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j)
-            if (gmn + j < MN) x[j] = q[j];
-        }
-      }
-    }
-    v[r] = x;
-  }
-}
-
-template <int BMN, bool KC>
-__device__ __forceinline__ void store_tile(float* __restrict__ s, const f32x4 (&v)[BMN / 64]) {
-  constexpr int S = BMN + 16;
-#pragma unroll
-  for (int r = 0; r < BMN / 64; ++r) {
-    int mn, k;
-    tile_coord<BMN, KC>(r, mn, k);
-    if (KC) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) s[(k + j) * S + mn] = v[r][j];
-    } else {
-      *(f32x4*)&s[k * S + mn] = v[r];
-    }
-  }
-}
-
 // T: 16x16 MFMA tiles per wave and dimension (2: 64x64 workgroup tile, 4: 128x128)
 template <int MODE, int T>
 __global__ __launch_bounds__(kThreads) void shared_gemm_kernel(const SharedP p) {
   constexpr int BT = 32 * T;     // workgroup tile edge
-  constexpr int S = BT + 16;     // LDS row pitch
   constexpr bool A_KC = MODE != MODE_UPD, B_KC = MODE == MODE_BWD;
-  __shared__ __attribute__((aligned(16))) float sA[2][kBK * S];
-  __shared__ __attribute__((aligned(16))) float sB[2][kBK * S];
 
   // blockIdx -> (instance or slice, tile-row, tile-col): one instance's tiles are consecutive
   const int z = (int)blockIdx.x / p.tiles, rem = (int)blockIdx.x % p.tiles;
-  const int bm = (rem / p.tn) * BT, bn = (rem % p.tn) * BT;
   int inst = z, K = p.K;
   long krow0 = 0;
   if (MODE == MODE_UPD) {
@@ -134,112 +57,18 @@ __global__ __launch_bounds__(kThreads) void shared_gemm_kernel(const SharedP p) 
     krow0 = (long)(z % p.kslices) * p.kchunk;
     K = min(p.kchunk, p.K - (int)krow0);
   }
+  TileWork w;
   // window bases: KC operands index [mn][k] from `base`, MC operands [k][mn]
-  const float* A = p.A + (long)inst * p.a_step + (A_KC ? 0 : krow0 * p.lda);
-  const float* B = p.B + (long)inst * p.b_step + (B_KC ? 0 : krow0 * p.ldb);
-
-  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
-  const int wm = (wave >> 1) * 16 * T, wn = (wave & 1) * 16 * T;
-  const int l15 = lane & 15, lk = lane >> 4;
-
-  f32x4 acc[T][T];
-#pragma unroll
-  for (int a = 0; a < T; ++a)
-#pragma unroll
-    for (int b = 0; b < T; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // update: the first tile-row's workgroups also sum the columns of their E tile (thread c: column bn + c):
-  // fp32 inside a 32-row slab, fp64 across slabs
-  const bool colsum = MODE == MODE_UPD && bm == 0 && (int)threadIdx.x < BT;
-  float cs = 0.f;
-  double cd = 0.0;
-
-  f32x4 ra[BT / 64], rb[BT / 64];
-  const int nk = (K + kBK - 1) / kBK;
-  load_tile<BT, A_KC>(A, p.lda, bm, p.M, 0, K, p.vecA, ra);
-  load_tile<BT, B_KC>(B, p.ldb, bn, p.N, 0, K, p.vecB, rb);
-  store_tile<BT, A_KC>(sA[0], ra);
-  store_tile<BT, B_KC>(sB[0], rb);
-  __syncthreads();
-  for (int kt = 0; kt < nk; ++kt) {
-    const int buf = kt & 1;
-    if (kt + 1 < nk) {
-      load_tile<BT, A_KC>(A, p.lda, bm, p.M, (kt + 1) * kBK, K, p.vecA, ra);
-      load_tile<BT, B_KC>(B, p.ldb, bn, p.N, (kt + 1) * kBK, K, p.vecB, rb);
-    }
-    const float* a_s = sA[buf];
-    const float* b_s = sB[buf];
-#pragma unroll
-    for (int s = 0; s < kBK / 4; ++s) {
-      const int kk = s * 4 + lk;
-      float av[T], bv[T];
-#pragma unroll
-      for (int a = 0; a < T; ++a) av[a] = a_s[kk * S + wm + a * 16 + l15];
-#pragma unroll
-      for (int b = 0; b < T; ++b) bv[b] = b_s[kk * S + wn + b * 16 + l15];
-#pragma unroll
-      for (int a = 0; a < T; ++a)
-#pragma unroll
-        for (int b = 0; b < T; ++b) acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[a][b], 0, 0, 0);
-    }
-    if (MODE == MODE_UPD) {
-      if (colsum) {
-#pragma unroll
-        for (int k = 0; k < kBK; ++k) cs += b_s[k * S + (int)threadIdx.x];
-        if ((kt & (kSlab / kBK - 1)) == kSlab / kBK - 1) {
-          cd += (double)cs;
-          cs = 0.f;
-        }
-      }
-    }
-    if (kt + 1 < nk) {  // the other buffer: last read before the barrier that ended iteration kt - 1
-      store_tile<BT, A_KC>(sA[buf ^ 1], ra);
-      store_tile<BT, B_KC>(sB[buf ^ 1], rb);
-    }
-    __syncthreads();
-  }
-
-  // epilogue: accumulator register r of MFMA tile (a, b) is row 4 * (lane >> 4) + r, column lane & 15
-  if (MODE == MODE_UPD) {
-    float* P = p.part + (long)z * p.pslab;
-#pragma unroll
-    for (int a = 0; a < T; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = bm + wm + a * 16 + lk * 4 + r;
-        if (row >= p.M) continue;
-#pragma unroll
-        for (int b = 0; b < T; ++b) {
-          const int col = bn + wn + b * 16 + l15;
-          if (col < p.N) P[(long)row * p.ldp + col] = acc[a][b][r];
-        }
-      }
-    if (colsum) {
-      cd += (double)cs;
-      const int col = bn + (int)threadIdx.x;
-      if (col < p.N) p.bpart[(long)z * p.ldbp + col] = cd;
-    }
-  } else {
-    float* C = p.C + (long)inst * p.c_step;
-    float bias_v[T];
-#pragma unroll
-    for (int b = 0; b < T; ++b) {
-      const int col = bn + wn + b * 16 + l15;
-      bias_v[b] = (MODE == MODE_FWD && col < p.N) ? p.bias[col] : 0.f;
-    }
-#pragma unroll
-    for (int a = 0; a < T; ++a)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = bm + wm + a * 16 + lk * 4 + r;
-        if (row >= p.M) continue;
-#pragma unroll
-        for (int b = 0; b < T; ++b) {
-          const int col = bn + wn + b * 16 + l15;
-          if (col < p.N) C[(long)row * p.ldc + col] = MODE == MODE_FWD ? acc[a][b][r] + bias_v[b] : acc[a][b][r];
-        }
-      }
-  }
+  w.A = p.A + (long)inst * p.a_step + (A_KC ? 0 : krow0 * p.lda); w.lda = p.lda;
+  w.B = p.B + (long)inst * p.b_step + (B_KC ? 0 : krow0 * p.ldb); w.ldb = p.ldb;
+  w.M = p.M; w.N = p.N; w.K = K;
+  w.bm = (rem / p.tn) * BT; w.bn = (rem % p.tn) * BT;
+  w.vecA = p.vecA; w.vecB = p.vecB;
+  w.C = p.C + (long)inst * p.c_step; w.ldc = p.ldc;
+  w.bias = p.bias;
+  w.P = p.part + (long)z * p.pslab; w.ldp = p.ldp;
+  w.bp = p.bpart + (long)z * p.ldbp;
+  tile_gemm<MODE, T>(w);
 }
 
 // The update's second launch.  Element (row, col) of W: the slices' partial products added in slice order
@@ -282,46 +111,11 @@ __global__ __launch_bounds__(kThreads) void shared_combine_kernel(const float* _
   }
 }
 
-// per-stream workspace of the update's partial products (grown on demand, reused launch after launch: the
-// library enqueues a stream's work in order -- gemm_f32.hip's split-K workspace has the same rule)
-std::mutex g_ws_mu;
-std::map<hipStream_t, std::pair<void*, size_t>> g_ws;
-void* shared_workspace(size_t bytes, hipStream_t st) {
-  std::lock_guard<std::mutex> lk(g_ws_mu);
-  auto& w = g_ws[st];
-  if (bytes > w.second) {
-    if (w.first) {
-      if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
-      (void)hipFree(w.first);
-      w = {nullptr, 0};
-    }
-    void* q = nullptr;
-    if (hipMalloc(&q, bytes) != hipSuccess) return nullptr;
-    w = {q, bytes};
-  }
-  return w.first;
-}
-
-bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-bool aligned4(const void* q) { return ((uintptr_t)q & 3) == 0; }
-bool dim_ok(const void* q, TnetMatrixDim d) {
-  return q && aligned4(q) && d.rows >= 0 && d.cols >= 1 && d.stride >= d.cols && (d.stride & 3) == 0;
-}
-bool overlap(const void* a, TnetMatrixDim da, const void* b, TnetMatrixDim db) {
-  if (!a || !b || da.rows <= 0 || db.rows <= 0) return false;
-  const char *a0 = (const char*)a, *b0 = (const char*)b;
-  const size_t na = (size_t)da.rows * (size_t)da.stride * 4, nb = (size_t)db.rows * (size_t)db.stride * 4;
-  return a0 < b0 + nb && b0 < a0 + na;
-}
 // 16-byte loads of an operand whose windows start `step` columns apart: the base and every origin aligned
 // (the strides are multiples of 4 by the entry points' argument checks)
 int vec_ok(const void* q, int step, int n_inst) { return aligned16(q) && (n_inst == 1 || (step & 3) == 0); }
 
-// 128x128 tiles where they still give every CU a workgroup, else 64x64
-int pick_tile(int M, int N, long batch) {
-  const long big = (long)cdiv(M, 128) * cdiv(N, 128) * batch;
-  return big >= 200 ? 4 : 2;
-}
+int pick_tile(int M, int N, long batch) { return pick_tile_count((long)cdiv(M, 128) * cdiv(N, 128) * batch); }
 
 // Shape class routed to the per-instance loop (measured, tools/shared_bench.py / profiles/shared_linearity.json):
 // where one instance's product alone fills the GPU (rows * in * out >= 2^28 multiply-adds, e.g. bunch 1024,
@@ -347,6 +141,25 @@ int launch_tiles(SharedP& p, long batch, hipStream_t st) {
 }
 
 }  // namespace
+
+void* tile_workspace(size_t bytes, hipStream_t st) {
+  static std::mutex mu;
+  static std::map<hipStream_t, std::pair<void*, size_t>> ws;
+  std::lock_guard<std::mutex> lk(mu);
+  auto& w = ws[st];
+  if (bytes > w.second) {
+    if (w.first) {
+      if (hipStreamSynchronize(st) != hipSuccess) return nullptr;
+      (void)hipFree(w.first);
+      w = {nullptr, 0};
+    }
+    void* q = nullptr;
+    if (hipMalloc(&q, bytes) != hipSuccess) return nullptr;
+    w = {q, bytes};
+  }
+  return w.first;
+}
+
 }  // namespace tnetk
 
 using namespace tnetk;
@@ -436,7 +249,7 @@ extern "C" int tnet_shared_update(const float* X, TnetMatrixDim dX, const float*
   p.pslab = (long)p.M * p.ldp;
   p.ldbp = p.N;
   const size_t bbytes = (((size_t)Z * p.ldbp * sizeof(double)) + 255) & ~(size_t)255;
-  char* ws = (char*)shared_workspace(bbytes + (size_t)Z * p.pslab * sizeof(float), st);
+  char* ws = (char*)tile_workspace(bbytes + (size_t)Z * p.pslab * sizeof(float), st);
   if (!ws) return TNET_ERR_RUNTIME;
   p.bpart = (double*)ws;
   p.part = (float*)(ws + bbytes);

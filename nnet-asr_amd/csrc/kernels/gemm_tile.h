@@ -1,0 +1,258 @@
+// gemm_tile.h -- the fp32 MFMA tile core shared by the instance-batched (gemm_shared.hip) and the grouped
+// (gemm_discrete.hip) GEMM kernels.  A kernel works out, from blockIdx, which operand windows and which output
+// tile its workgroup owns (TileWork) and calls tile_gemm: 256 threads = 2 x 2 waves on
+// v_mfma_f32_16x16x4_f32 (fp32 in / fp32 accumulate), a 64x64 or 128x128 output tile, k-tiles of 16 staged
+// through a double-buffered LDS image [k][m or n] (row pitch tile + 16 floats: the four k rows a wave's MFMA
+// operand read touches fall on disjoint banks), the next k-tile's global loads in flight while the current one
+// is multiplied.  An operand is read with 16-byte loads where its window allows it and through a masked scalar
+// path otherwise; out-of-range elements are never read (they enter the product as zeros) and never stored.
+#pragma once
+#include "kcommon.h"
+
+namespace tnetk {
+
+constexpr int kBK = 16;       // k-tile depth
+constexpr int kThreads = 256; // 2 x 2 waves
+constexpr int kSlab = 32;     // rows whose column sum stays in fp32 (the project's slab size)
+
+enum { MODE_FWD = 0, MODE_BWD = 1, MODE_UPD = 2 };
+
+// One workgroup's job.  MODE_FWD: C = A B + bias (A [M x K] k contiguous, B [K x N] n contiguous);
+// MODE_BWD: C = A B^T (B given as [N x K], k contiguous); MODE_UPD: P = A^T B over K rows (A [K x M],
+// B [K x N]) and, in the first tile-row's workgroups, the column sums of B into bp.
+struct TileWork {
+  const float* A; long lda;
+  const float* B; long ldb;
+  int M, N, K;
+  int bm, bn;                 // the tile's origin in the [M x N] output
+  int vecA, vecB;             // 16-byte loads allowed
+  float* C; long ldc;         // fwd / bwd: output window
+  const float* bias;          // fwd: the window's bias
+  float* P; long ldp;         // update: this slice's partial product
+  double* bp;                 // update: this slice's partial column sums of B
+};
+
+// One thread's share of a [BMN x 16] operand tile: BMN / 64 groups of four elements.
+//   KC (k contiguous in memory: elem(mn, k) = base[mn * ld + k]): the four are consecutive k of one row
+//   MC (mn contiguous:          elem(mn, k) = base[k * ld + mn]): the four are consecutive mn of one k row
+template <int BMN, bool KC>
+__device__ __forceinline__ void tile_coord(int r, int& mn, int& k) {
+  const int e = (int)threadIdx.x + kThreads * r;
+  if (KC) {
+    mn = e >> 2;
+    k = (e & 3) * 4;
+  } else {
+    k = e / (BMN / 4);
+    mn = (e % (BMN / 4)) * 4;
+  }
+}
+
+template <int BMN, bool KC>
+__device__ __forceinline__ void load_tile(const float* __restrict__ base, long ld, int mn0, int MN, int k0, int K,
+                                          int vec, f32x4 (&v)[BMN / 64]) {
+#pragma unroll
+  for (int r = 0; r < BMN / 64; ++r) {
+    int mn, k;
+    tile_coord<BMN, KC>(r, mn, k);
+    const int gmn = mn0 + mn, gk = k0 + k;
+    f32x4 x = {0.f, 0.f, 0.f, 0.f};
+    if (KC) {
+      if (gmn < MN && gk < K) {
+        const float* q = base + (long)gmn * ld + gk;
+        if (vec && gk + 3 < K) {
+          x = *(const f32x4*)q;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (gk + j < K) x[j] = q[j];
+        }
+      }
+    } else {
+      if (gk < K && gmn < MN) {
+        const float* q = base + (long)gk * ld + gmn;
+        if (vec && gmn + 3 < MN) {
+          x = *(const f32x4*)q;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (gmn + j < MN) x[j] = q[j];
+        }
+      }
+    }
+    v[r] = x;
+  }
+}
+
+template <int BMN, bool KC>
+__device__ __forceinline__ void store_tile(float* __restrict__ s, const f32x4 (&v)[BMN / 64]) {
+  constexpr int S = BMN + 16;
+#pragma unroll
+  for (int r = 0; r < BMN / 64; ++r) {
+    int mn, k;
+    tile_coord<BMN, KC>(r, mn, k);
+    if (KC) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s[(k + j) * S + mn] = v[r][j];
+    } else {
+      *(f32x4*)&s[k * S + mn] = v[r];
+    }
+  }
+}
+
+// T: 16x16 MFMA tiles per wave and dimension (2: 64x64 workgroup tile, 4: 128x128)
+// PF: k-tiles whose global loads are in flight while one is multiplied (register stages; the LDS image stays
+// double-buffered).  1 hides a load behind one k-tile's MFMAs, which is enough where several workgroups share a
+// CU; 2 is for grids of few workgroups with deep K, where one k-tile's work is shorter than the load latency.
+template <int MODE, int T, int PF = 1>
+__device__ __forceinline__ void tile_gemm(const TileWork& w) {
+  static_assert(PF == 1 || PF == 2, "the LDS buffer index below assumes PF divides 2");
+  constexpr int BT = 32 * T;     // workgroup tile edge
+  constexpr int S = BT + 16;     // LDS row pitch
+  constexpr bool A_KC = MODE != MODE_UPD, B_KC = MODE == MODE_BWD;
+  __shared__ __attribute__((aligned(16))) float sA[2][kBK * S];
+  __shared__ __attribute__((aligned(16))) float sB[2][kBK * S];
+
+  const float* A = w.A;
+  const float* B = w.B;
+  const int bm = w.bm, bn = w.bn, K = w.K;
+
+  const int lane = (int)threadIdx.x & 63, wave = (int)threadIdx.x >> 6;
+  const int wm = (wave >> 1) * 16 * T, wn = (wave & 1) * 16 * T;
+  const int l15 = lane & 15, lk = lane >> 4;
+
+  f32x4 acc[T][T];
+#pragma unroll
+  for (int a = 0; a < T; ++a)
+#pragma unroll
+    for (int b = 0; b < T; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // update: the first tile-row's workgroups also sum the columns of their E tile (thread c: column bn + c):
+  // fp32 inside a 32-row slab, fp64 across slabs
+  const bool colsum = MODE == MODE_UPD && bm == 0 && (int)threadIdx.x < BT;
+  float cs = 0.f;
+  double cd = 0.0;
+
+  // register stage t % PF holds k-tile t from its load until it is stored to LDS at the end of iteration t - 1
+  f32x4 ra[PF][BT / 64], rb[PF][BT / 64];
+  const int nk = (K + kBK - 1) / kBK;
+  load_tile<BT, A_KC>(A, w.lda, bm, w.M, 0, K, w.vecA, ra[0]);
+  load_tile<BT, B_KC>(B, w.ldb, bn, w.N, 0, K, w.vecB, rb[0]);
+  store_tile<BT, A_KC>(sA[0], ra[0]);
+  store_tile<BT, B_KC>(sB[0], rb[0]);
+#pragma unroll
+  for (int t = 1; t < PF; ++t)
+    if (t < nk) {
+      load_tile<BT, A_KC>(A, w.lda, bm, w.M, t * kBK, K, w.vecA, ra[t]);
+      load_tile<BT, B_KC>(B, w.ldb, bn, w.N, t * kBK, K, w.vecB, rb[t]);
+    }
+  __syncthreads();
+  for (int kt0 = 0; kt0 < nk; kt0 += PF) {
+#pragma unroll
+    for (int u = 0; u < PF; ++u) {  // unrolled: the stage indices are compile-time constants
+      const int kt = kt0 + u;
+      if (kt >= nk) break;
+      const int buf = PF == 1 ? (kt & 1) : (u & 1);
+      if (kt + PF < nk) {  // stage u is free: k-tile kt left it for LDS an iteration ago
+        load_tile<BT, A_KC>(A, w.lda, bm, w.M, (kt + PF) * kBK, K, w.vecA, ra[u]);
+        load_tile<BT, B_KC>(B, w.ldb, bn, w.N, (kt + PF) * kBK, K, w.vecB, rb[u]);
+      }
+      const float* a_s = sA[buf];
+      const float* b_s = sB[buf];
+#pragma unroll
+      for (int s = 0; s < kBK / 4; ++s) {
+        const int kk = s * 4 + lk;
+        float av[T], bv[T];
+#pragma unroll
+        for (int a = 0; a < T; ++a) av[a] = a_s[kk * S + wm + a * 16 + l15];
+#pragma unroll
+        for (int b = 0; b < T; ++b) bv[b] = b_s[kk * S + wn + b * 16 + l15];
+#pragma unroll
+        for (int a = 0; a < T; ++a)
+#pragma unroll
+          for (int b = 0; b < T; ++b)
+            acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[a], bv[b], acc[a][b], 0, 0, 0);
+      }
+      if (MODE == MODE_UPD) {
+        if (colsum) {
+#pragma unroll
+          for (int k = 0; k < kBK; ++k) cs += b_s[k * S + (int)threadIdx.x];
+          if ((kt & (kSlab / kBK - 1)) == kSlab / kBK - 1) {
+            cd += (double)cs;
+            cs = 0.f;
+          }
+        }
+      }
+      if (kt + 1 < nk) {  // the other buffer: last read before the barrier that ended iteration kt - 1
+        store_tile<BT, A_KC>(sA[buf ^ 1], ra[(u + 1) % PF]);
+        store_tile<BT, B_KC>(sB[buf ^ 1], rb[(u + 1) % PF]);
+      }
+      __syncthreads();
+    }
+  }
+
+  // epilogue: accumulator register r of MFMA tile (a, b) is row 4 * (lane >> 4) + r, column lane & 15
+  if (MODE == MODE_UPD) {
+    float* P = w.P;
+#pragma unroll
+    for (int a = 0; a < T; ++a)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = bm + wm + a * 16 + lk * 4 + r;
+        if (row >= w.M) continue;
+#pragma unroll
+        for (int b = 0; b < T; ++b) {
+          const int col = bn + wn + b * 16 + l15;
+          if (col < w.N) P[(long)row * w.ldp + col] = acc[a][b][r];
+        }
+      }
+    if (colsum) {
+      cd += (double)cs;
+      const int col = bn + (int)threadIdx.x;
+      if (col < w.N) w.bp[col] = cd;
+    }
+  } else {
+    float* C = w.C;
+    float bias_v[T];
+#pragma unroll
+    for (int b = 0; b < T; ++b) {
+      const int col = bn + wn + b * 16 + l15;
+      bias_v[b] = (MODE == MODE_FWD && col < w.N) ? w.bias[col] : 0.f;
+    }
+#pragma unroll
+    for (int a = 0; a < T; ++a)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = bm + wm + a * 16 + lk * 4 + r;
+        if (row >= w.M) continue;
+#pragma unroll
+        for (int b = 0; b < T; ++b) {
+          const int col = bn + wn + b * 16 + l15;
+          if (col < w.N) C[(long)row * w.ldc + col] = MODE == MODE_FWD ? acc[a][b][r] + bias_v[b] : acc[a][b][r];
+        }
+      }
+  }
+}
+
+// argument checks and tile choice common to both files' entry points
+inline bool aligned16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+inline bool aligned4(const void* q) { return ((uintptr_t)q & 3) == 0; }
+inline bool dim_ok(const void* q, TnetMatrixDim d) {
+  return q && aligned4(q) && d.rows >= 0 && d.cols >= 1 && d.stride >= d.cols && (d.stride & 3) == 0;
+}
+inline bool overlap_bytes(const void* a, size_t na, const void* b, size_t nb) {
+  if (!a || !b || !na || !nb) return false;
+  const char *a0 = (const char*)a, *b0 = (const char*)b;
+  return a0 < b0 + nb && b0 < a0 + na;
+}
+inline bool overlap(const void* a, TnetMatrixDim da, const void* b, TnetMatrixDim db) {
+  if (da.rows <= 0 || db.rows <= 0) return false;
+  return overlap_bytes(a, (size_t)da.rows * (size_t)da.stride * 4, b, (size_t)db.rows * (size_t)db.stride * 4);
+}
+// 128x128 tiles where `big` of them still give every CU a workgroup, else 64x64
+inline int pick_tile_count(long big) { return big >= 200 ? 4 : 2; }
+
+// per-stream workspace of an update's partial products (grown on demand, reused launch after launch: the
+// library enqueues a stream's work in order -- gemm_f32.hip's split-K workspace has the same rule)
+void* tile_workspace(size_t bytes, hipStream_t st);
+
+}  // namespace tnetk

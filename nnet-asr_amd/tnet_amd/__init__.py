@@ -109,6 +109,54 @@ class DeviceArray:
             pass
 
 
+class DiscretePlan:
+    """TnetDiscretePlan (include/tnet_kernels.h): the packed parameter layout and device tables of the grouped
+    <discretelinearity> kernels for blocks [(in_k, out_k), ...]."""
+
+    def __init__(self, blocks: Sequence):
+        self.blocks = [(int(a), int(b)) for a, b in blocks]
+        ni = np.array([a for a, _ in self.blocks], np.int32)
+        no = np.array([b for _, b in self.blocks], np.int32)
+        p = C.c_void_p()
+        check(lib().tnet_discrete_plan_create(ni.ctypes.data, no.ctypes.data, len(self.blocks), C.byref(p)),
+              "discrete_plan_create")
+        self.ptr = p.value
+        self.floats = int(lib().tnet_discrete_plan_floats(self.ptr))
+        self.layout = []                       # (offset, row stride) per block
+        for k in range(len(self.blocks)):
+            off, ld = C.c_long(), C.c_int()
+            check(lib().tnet_discrete_plan_block(self.ptr, k, C.byref(off), C.byref(ld)), "discrete_plan_block")
+            self.layout.append((off.value, ld.value))
+
+    def pack(self, Ws, fill: float = 0.0) -> np.ndarray:
+        """the blocks [in_k x out_k] in the packed layout (the stride padding holds `fill`)"""
+        out = np.full(self.floats, fill, np.float32)
+        for W, (ni, no), (off, ld) in zip(Ws, self.blocks, self.layout):
+            out[off:off + ni * ld].reshape(ni, ld)[:, :no] = np.asarray(W, np.float32).reshape(ni, no)
+        return out
+
+    def unpack(self, packed: np.ndarray):
+        packed = np.asarray(packed).reshape(-1)
+        return [packed[off:off + ni * ld].reshape(ni, ld)[:, :no].copy()
+                for (ni, no), (off, ld) in zip(self.blocks, self.layout)]
+
+    def padding(self, packed: np.ndarray) -> np.ndarray:
+        """the stride-padding elements of a packed buffer"""
+        packed = np.asarray(packed).reshape(-1)
+        parts = [packed[off:off + ni * ld].reshape(ni, ld)[:, no:].reshape(-1)
+                 for (ni, no), (off, ld) in zip(self.blocks, self.layout)]
+        return np.concatenate(parts)
+
+    def __del__(self):
+        try:
+            if getattr(self, "ptr", None):
+                lib().tnet_synchronize()
+                lib().tnet_discrete_plan_free(self.ptr)
+                self.ptr = None
+        except Exception:
+            pass
+
+
 class Network:
     """CuNetwork (src/CuTNetLib/cuNetwork.h:22-194) handle."""
 
@@ -214,6 +262,44 @@ class Network:
                 raise ValueError("set_shared_params: shape mismatch")
         check(lib().tnet_net_shared_set(self.h, i, None if W is None else W.ctypes.data,
                                         None if b is None else b.ctypes.data), "shared_set")
+
+    def discrete_blocks(self, i: int = 0):
+        """[(in_k, out_k), ...] of a <discretelinearity> component."""
+        n = C.c_int()
+        check(lib().tnet_net_discrete_blocks(self.h, i, C.byref(n), None, None), "discrete_blocks")
+        ni, no = np.zeros(n.value, np.int32), np.zeros(n.value, np.int32)
+        check(lib().tnet_net_discrete_blocks(self.h, i, None, ni.ctypes.data, no.ctypes.data), "discrete_blocks")
+        return [(int(a), int(b)) for a, b in zip(ni, no)]
+
+    def discrete_params(self, i: int = 0):
+        """([W_k [in_k x out_k], ...], bias [n_out]) of a <discretelinearity> component."""
+        Ws = []
+        for k, (ni, no) in enumerate(self.discrete_blocks(i)):
+            W = np.empty((ni, no), np.float32)
+            check(lib().tnet_net_discrete_get(self.h, i, k, W.ctypes.data, None), "discrete_get")
+            Ws.append(W)
+        b = np.empty(self.components()[i][2], np.float32)
+        check(lib().tnet_net_discrete_get(self.h, i, 0, None, b.ctypes.data), "discrete_get")
+        return Ws, b
+
+    def set_discrete_params(self, i: int, Ws=None, b=None) -> None:
+        """Ws: a list with one [in_k x out_k] array (or None: keep) per block; b: the bias or None."""
+        blocks = self.discrete_blocks(i)
+        if Ws is not None:
+            if len(Ws) != len(blocks):
+                raise ValueError("set_discrete_params: block count mismatch")
+            for k, (W, shape) in enumerate(zip(Ws, blocks)):
+                if W is None:
+                    continue
+                W = np.ascontiguousarray(W, np.float32)
+                if W.shape != shape:
+                    raise ValueError("set_discrete_params: shape mismatch")
+                check(lib().tnet_net_discrete_set(self.h, i, k, W.ctypes.data, None), "discrete_set")
+        if b is not None:
+            b = np.ascontiguousarray(b, np.float32)
+            if b.shape != (self.components()[i][2],):
+                raise ValueError("set_discrete_params: shape mismatch")
+            check(lib().tnet_net_discrete_set(self.h, i, 0, None, b.ctypes.data), "discrete_set")
 
     def rbm_params(self, i: int = 0):
         """(W [n_vis x n_hid], vis_bias, hid_bias, (vis_type, hid_type)) of an <rbm> component."""

@@ -112,6 +112,15 @@ _SIGS = {
     "tnet_shared_bwd": (i32, [vp, MatrixDim, vp, MatrixDim, i32, vp, MatrixDim, vp]),
     "tnet_shared_update": (i32, [vp, MatrixDim, vp, MatrixDim, i32, vp, MatrixDim, vp, i32, vp, vp, f32, f32, f32,
                                  vp]),
+    "tnet_discrete_plan_create": (i32, [vp, vp, i32, C.POINTER(vp)]),
+    "tnet_discrete_plan_free": (i32, [vp]),
+    "tnet_discrete_plan_floats": (i64, [vp]),
+    "tnet_discrete_plan_blocks": (i32, [vp]),
+    "tnet_discrete_plan_block": (i32, [vp, i32, C.POINTER(i64), C.POINTER(i32)]),
+    "tnet_discrete_loop_routing": (i32, [i32]),
+    "tnet_discrete_fwd": (i32, [vp, MatrixDim, vp, vp, vp, vp, MatrixDim, vp]),
+    "tnet_discrete_bwd": (i32, [vp, MatrixDim, vp, vp, vp, MatrixDim, vp]),
+    "tnet_discrete_update": (i32, [vp, MatrixDim, vp, MatrixDim, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
     "tnet_sgd_update": (i32, [vp, vp, vp, i64, f32, f32, f32, vp]),
     "tnet_bias_update": (i32, [vp, MatrixDim, vp, vp, vp, f32, f32, vp, vp]),
     "tnet_softmax_xent": (i32, [vp, MatrixDim, vp, vp, i32, vp, i32, vp, vp]),
@@ -213,6 +222,9 @@ _SIGS = {
     "tnet_net_recurrent_set": (i32, [vp, i32, vp, vp]),
     "tnet_net_shared_get": (i32, [vp, i32, vp, vp, vp]),
     "tnet_net_shared_set": (i32, [vp, i32, vp, vp]),
+    "tnet_net_discrete_blocks": (i32, [vp, i32, vp, vp, vp]),
+    "tnet_net_discrete_get": (i32, [vp, i32, i32, vp, vp]),
+    "tnet_net_discrete_set": (i32, [vp, i32, i32, vp, vp]),
     "tnet_rnn_trainer_create": (vp, [vp, vp, i32, i32]),
     "tnet_rnn_trainer_free": (i32, [vp]),
     "tnet_rnn_trainer_utterance": (i32, [vp, vp, i32, i32, i32, vp]),

@@ -78,6 +78,18 @@ def _write_layers(out, layers: Sequence[Layer], precision: int) -> None:
             b = np.asarray(L.b, dtype=np.float32)
             out.write(f"v {b.shape[0]}  " + " ".join(_fmt(v, precision) for v in b) + " ")
             out.write("\n\n")
+        elif L.tag == "<discretelinearity>":     # cuDiscreteLinearity.cc:139-156: count, transposed blocks, bias
+            Ws = L.extra["Ws"]
+            out.write(f"{len(Ws)}\n")
+            for W in Ws:
+                Wt = np.asarray(W, dtype=np.float32).T
+                out.write(f"m {Wt.shape[0]} {Wt.shape[1]}\n")
+                for row in Wt:
+                    out.write(" ".join(_fmt(v, precision) for v in row))
+                    out.write(" \n")
+            b = np.asarray(L.b, dtype=np.float32)
+            out.write(f"v {b.shape[0]}  " + " ".join(_fmt(v, precision) for v in b) + " ")
+            out.write("\n\n")
         elif L.tag == "<blockarray>":            # cuBlockArray.cc:125-135
             blocks = L.extra["blocks"]
             out.write(f" {len(blocks)} ")
@@ -178,6 +190,25 @@ def read_nnet(path_or_text: str) -> List[Layer]:
                 L.b = read_vector()
                 if L.W.shape != (n_in // n, n_out // n) or L.b.shape != (n_out // n,):
                     raise ValueError("Wrong dimensionalities of matrix/vector in network file")
+            elif tag == "<discretelinearity>":
+                # cuDiscreteLinearity.cc:81-136 and its error conditions
+                nb = int(toks[i])
+                i += 1
+                if nb < 1:
+                    raise ValueError(f"Bad number of blocks:{nb}")
+                Ws = []
+                for _ in range(nb):
+                    Wt = read_matrix()
+                    if Wt.size == 0:
+                        raise ValueError("Missing linearity matrix in network file")
+                    Ws.append(np.ascontiguousarray(Wt.T))
+                L.b = read_vector()
+                if L.b.size == 0:
+                    raise ValueError("Missing bias vector in network file")
+                if (sum(W.shape[1] for W in Ws) != n_out or sum(W.shape[0] for W in Ws) != n_in
+                        or L.b.shape[0] != n_out):
+                    raise ValueError("Wrong dimensionalities of matrix/vector in network file")
+                L.extra["Ws"] = Ws
             elif tag == "<blockarray>":
                 # cuBlockArray.cc:57-122
                 nb = int(toks[i])
@@ -282,6 +313,29 @@ def gen_shared_init(n_inst: int, n_in: int, n_out: int, seed: int, gauss: bool =
     return [Layer("<sharedlinearity>", n_inst * n_out, n_inst * n_in, np.ascontiguousarray(Wt.T), b,
                   {"n_inst": int(n_inst)}),
             Layer("<sigmoid>", n_inst * n_out, n_inst * n_out)]
+
+
+def gen_discrete_init(dims_in: Sequence[int], dims_out: Sequence[int], seed: int, gauss: bool = True,
+                      negbias: bool = True) -> List[Layer]:
+    """One <discretelinearity> of len(dims_in) blocks, block k a dims_in[k] -> dims_out[k] transform (the layer is
+    sum(dims_in) -> sum(dims_out); tools/init/gen_discretelinearity_init.py writes equal blocks, the file format
+    allows ragged ones) followed by its <sigmoid>, parameters drawn as gen_mlp_init draws a hidden layer's: every
+    W_k^T ~ 0.1 N(0,1) (--gauss) or U[-0.1, 0.1] in block order, then the bias U[-4.1, -3.9] (--negbias) or 0.
+    Layer.W is None; the blocks are extra["Ws"]."""
+    if len(dims_in) != len(dims_out) or not len(dims_in):
+        raise ValueError("gen_discrete_init: one input and one output size per block")
+    rng = np.random.default_rng(seed)
+    Ws = []
+    for n_in, n_out in zip(dims_in, dims_out):
+        if gauss:
+            Wt = (0.1 * rng.standard_normal((n_out, n_in))).astype(np.float32)
+        else:
+            Wt = (rng.random((n_out, n_in)) / 5.0 - 0.1).astype(np.float32)
+        Ws.append(np.ascontiguousarray(Wt.T))
+    n_out, n_in = int(sum(dims_out)), int(sum(dims_in))
+    b = (rng.random(n_out) / 5.0 - 4.1).astype(np.float32) if negbias else np.zeros(n_out, np.float32)
+    return [Layer("<discretelinearity>", n_out, n_in, None, b, {"Ws": Ws}),
+            Layer("<sigmoid>", n_out, n_out)]
 
 
 def gen_recurrent_init(n_in: int, n_hid: int, n_out: int, seed: int, gauss: bool = True,
