@@ -577,6 +577,58 @@ int tnet_discrete_update(const float* X, TnetMatrixDim dX, const float* E, TnetM
                          const TnetDiscretePlan* plan, float* Wp, float* corrp, float* b, float* corr_b, float scale,
                          float mmt, float l2, void* stream);
 
+/* ---- <sparselinearity> (CuSparseLinearity, cuSparseLinearity.cc:11-97): a dense W [n_in x n_out] with a 0/1
+ * sparsity mask, a running sum `accu` of the momentum buffer and an L1 soft threshold.  Forward and backward are
+ * tnet_affine_fwd / tnet_affine_bwd (W holds exact zeros under the mask); these entry points are the update and the
+ * mask (gemm_sparse.hip).
+ *
+ * On the device the mask is a bit matrix: row r has ceil(n_out/32) uint32 words at a word stride ldmask, bit c & 31
+ * of word c >> 5 is the mask of W[r][c], bits at columns >= n_out are zero (words past ceil(n_out/32) are never
+ * touched).
+ *   tnet_sparse_mask_pack   : bits from a float matrix, nonzero -> 1
+ *   tnet_sparse_mask_unpack : the reverse, floats 0.0 / 1.0 (padding columns of maskf are not written)
+ *   tnet_sparse_update      : the whole of CuSparseLinearity::Update (cuSparseLinearity.cc:28-63: Gemm('T','N'),
+ *                             AddColSum, two AddScaled, the accu AddScaled, ApplyMask, ApplyL1 and the L2 AddScaled,
+ *                             cukernels.cu:34-62) except the frame count, per element in this order:
+ *                               c = X^T E + mmt*corrW ; corrW = c ; w = W + scale*c ; accu += c ;
+ *                               w = 0 where the mask is 0 ;
+ *                               l1c > 0: w = |w| < l1c ? 0 : (w > 0 ? w - l1c : w + l1c) ; l2 != 0: w = w + l2*w ; W = w
+ *                               cb = colsum(E) + mmt*corr_b ; corr_b = cb ; b += scale*cb
+ *                             The caller computes scale = -lr/N, l1c = lr*l1*(gdf?1:rows) and
+ *                             l2 = -lr*wc*(gdf?1:rows).  corrW and corr_b are required (accu needs the new corrW also
+ *                             when mmt == 0).  rows == 0 still applies momentum, mask, L1 and L2 with a zero
+ *                             gradient.  Any rows / n_in / n_out; pointers 4-byte aligned, strides multiples of 4
+ *                             elements; X and E are read with 16-byte loads where they are 16-byte aligned and
+ *                             through a masked scalar path otherwise.  Padding columns [cols, stride) of W, corrW
+ *                             and accu are never written.  No atomics: the same inputs give the same bits.
+ *                             Two forms: a single launch whose GEMM epilogue applies the arithmetic to the unsplit
+ *                             tile in the accumulators (mask word read once per row and 32 columns; bias from
+ *                             the first tile-row's workgroups, column sums fp32 inside a 32-row slab, fp64 across
+ *                             slabs), taken where the 64x64 tile grid has at least 512 tiles; below that the
+ *                             sliced form: K slices of `rows` into the per-stream workspace the library keeps and a
+ *                             second launch that adds them in slice order and applies the same arithmetic
+ *                             (measured: profiles/sparse_linearity.json).
+ *   tnet_sparse_update_form : force a form for later calls (0 automatic, 1 single launch, 2 sliced; | 0x20: 128x128
+ *                             tiles instead of 64x64, which lost in every measured cell and are never chosen
+ *                             automatically -- for tests and tools/sparse_bench.py); returns the previous setting.
+ *                             Not thread-safe.
+ *   tnet_sparse_mask_update : CuSparseLinearity::UpdateMask (cuSparseLinearity.cc:66-97, there three matrices
+ *                             copied to the host and back) in one element-wise launch, comparisons in fp32:
+ *                             mask 1 and fabsf(W) < sparsify_threshold: mask = 0, W = 0;
+ *                             mask 0 and fabsf(accu) / nframes > unsparsify_accu: mask = 1, W unchanged.
+ *                             One lane stores each mask word (a wavefront's ballot): no word has two writers.
+ * TNET_ERR_ARG before any launch: a NULL operand; dX.cols != dW.rows, dE.cols != dW.cols, dX.rows != dE.rows;
+ * a stride that is no multiple of 4 or below the column count; ldmask < ceil(n_out/32); W, corrW, accu or bits
+ * overlapping X or E or each other (pack / unpack / mask_update: their matrices overlapping bits or each other). */
+int tnet_sparse_mask_pack(const float* maskf, TnetMatrixDim d, unsigned* bits, int ldmask, void* stream);
+int tnet_sparse_mask_unpack(const unsigned* bits, int ldmask, float* maskf, TnetMatrixDim d, void* stream);
+int tnet_sparse_update(const float* X, TnetMatrixDim dX, const float* E, TnetMatrixDim dE, float* W, TnetMatrixDim dW,
+                       float* corrW, int ldcorr, float* accu, int ldaccu, const unsigned* bits, int ldmask, float* b,
+                       float* corr_b, float scale, float mmt, float l1c, float l2, void* stream);
+int tnet_sparse_update_form(int form);
+int tnet_sparse_mask_update(float* W, TnetMatrixDim dW, unsigned* bits, int ldmask, const float* accu, int ldaccu,
+                            float sparsify_threshold, float unsparsify_accu, float nframes, void* stream);
+
 /* ---- per-element HybridTaus random numbers (CuRand, curand.tcc / curandkernels.cu) ----------
  * z1..z4: four uint32 state arrays with the element layout of the target matrix (index =
  * col + row*stride), seeded by the caller with lrand48() values > 128 (curand.tcc:36-45) and

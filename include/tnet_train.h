@@ -225,6 +225,23 @@ int tnet_net_discrete_blocks(TnetNetwork* net, int i, int* n_blocks, int* n_in, 
 int tnet_net_discrete_get(TnetNetwork* net, int i, int blk, float* W, float* b);
 int tnet_net_discrete_set(TnetNetwork* net, int i, int blk, const float* W, const float* b);
 
+/* ---- <sparselinearity> (CuSparseLinearity, cuSparseLinearity.cc) ---------------------------------
+ * tnet_net_set_l1: CuNetwork::SetL1 (cuNetwork.cc:186-196, TNetCu's --L1): the L1 constant of every
+ * <sparselinearity> component, nothing else.
+ * get: W [n_in x n_out], the mask as 0/1 floats and accu (the running sum of the momentum buffer) of the same shape,
+ * host row-major; bias [n_out]; the frames seen since the layer was read.  set: W, bias, mask (nonzero -> 1; setting
+ * the mask does not touch W).  Any pointer may be NULL.
+ * thresholds: the sparsify weight threshold (default 1e-3) and the unsparsify accu threshold (default 1e20; the
+ * reference has no setter for either); a negative value leaves that threshold as it is.
+ * update_mask: CuSparseLinearity::UpdateMask (cuSparseLinearity.cc:66-97), which also runs at the start of every
+ * tnet_net_write.  Another component type is an error; tnet_net_get_params / tnet_net_set_params stay
+ * <biasedlinearity>-only. */
+int tnet_net_set_l1(TnetNetwork* net, float l1);
+int tnet_net_sparse_get(TnetNetwork* net, int i, float* W, float* b, float* mask, float* accu, long* nframes);
+int tnet_net_sparse_set(TnetNetwork* net, int i, const float* W, const float* b, const float* mask);
+int tnet_net_sparse_thresholds(TnetNetwork* net, int i, float sparsify_threshold, float unsparsify_accu);
+int tnet_net_sparse_update_mask(TnetNetwork* net, int i);
+
 /* ---- data parallel (no reference counterpart: Platform.h:143-391 is the CPU analogue) ---- */
 int tnet_comm_unique_id(char out[128]);        /* rank 0 creates, the launcher broadcasts it */
 TnetComm* tnet_comm_create(int rank, int world, const char id[128]);

@@ -10,6 +10,7 @@
 #include "curecurrent.h"
 #include "cudiscrete.h"
 #include "cushared.h"
+#include "cusparse.h"
 #include "htkio.h"
 #include "trainer.h"
 
@@ -701,6 +702,46 @@ int tnet_net_discrete_set(TnetNetwork* h, int i, int blk, const float* W, const 
   if (blk < 0 || blk >= L.NBlocks()) Error("block index out of range");
   if (W) L.SetBlock(blk, W, L.BlockOutputs(blk));
   if (b) L.Bias().CopyFromHost(b, L.Bias().Dim());
+  CuDevice::Instantiate().Synchronize();
+  TRY_END
+}
+
+// ----------------------------------------------------------------------- <sparselinearity>
+static CuSparseLinearity& sparse_layer(TnetNetwork* h, int i) {
+  if (i < 0 || i >= h->net.Layers()) Error("component index out of range");
+  auto* p = dynamic_cast<CuSparseLinearity*>(&h->net.Layer(i));
+  if (!p) Error("component is not <sparselinearity>");
+  return *p;
+}
+int tnet_net_set_l1(TnetNetwork* h, float l1) {
+  TRY_BEGIN h->net.SetL1(l1);
+  TRY_END
+}
+int tnet_net_sparse_get(TnetNetwork* h, int i, float* W, float* b, float* mask, float* accu, long* nframes) {
+  TRY_BEGIN CuSparseLinearity& L = sparse_layer(h, i);
+  if (W) L.Linearity().CopyToHost(W, L.Linearity().Cols());
+  if (b) L.Bias().CopyToHost(b);
+  if (mask) L.GetMask(mask, L.Linearity().Cols());
+  if (accu) L.Accu().CopyToHost(accu, L.Accu().Cols());
+  if (nframes) *nframes = L.NFrames();
+  TRY_END
+}
+int tnet_net_sparse_set(TnetNetwork* h, int i, const float* W, const float* b, const float* mask) {
+  TRY_BEGIN CuSparseLinearity& L = sparse_layer(h, i);
+  if (W) L.Linearity().CopyFromHost(W, L.Linearity().Rows(), L.Linearity().Cols(), L.Linearity().Cols());
+  if (b) L.Bias().CopyFromHost(b, L.Bias().Dim());
+  if (mask) L.SetMask(mask, L.Linearity().Cols());
+  CuDevice::Instantiate().Synchronize();
+  TRY_END
+}
+int tnet_net_sparse_thresholds(TnetNetwork* h, int i, float sparsify_threshold, float unsparsify_accu) {
+  TRY_BEGIN CuSparseLinearity& L = sparse_layer(h, i);
+  if (!(sparsify_threshold < 0.0f)) L.SparsifyWeightThreshold(sparsify_threshold);
+  if (!(unsparsify_accu < 0.0f)) L.UnsparsifyAccu(unsparsify_accu);
+  TRY_END
+}
+int tnet_net_sparse_update_mask(TnetNetwork* h, int i) {
+  TRY_BEGIN sparse_layer(h, i).UpdateMask();
   CuDevice::Instantiate().Synchronize();
   TRY_END
 }

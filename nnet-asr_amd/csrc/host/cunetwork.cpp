@@ -6,6 +6,7 @@
 #include "curecurrent.h"
 #include "cudiscrete.h"
 #include "cushared.h"
+#include "cusparse.h"
 
 #include <algorithm>
 #include <cctype>
@@ -134,8 +135,9 @@ void CuNetwork::SetWeightcost(BaseFloat weightcost) {
     if (c->IsUpdatable()) dynamic_cast<CuUpdatableComponent*>(c)->Weightcost(weightcost);
 }
 void CuNetwork::SetL1(BaseFloat l1) {
-  // only <sparselinearity> uses L1 (cuNetwork.cc:159-168); not part of this build's component set
-  (void)l1;
+  // only <sparselinearity> uses L1 (cuNetwork.cc:186-196)
+  for (auto* c : mNetComponents)
+    if (c->GetType() == CuComponent::SPARSE_LINEARITY) dynamic_cast<CuSparseLinearity*>(c)->L1(l1);
 }
 void CuNetwork::SetGradDivFrm(bool div) {
   for (auto* c : mNetComponents)
@@ -166,6 +168,8 @@ CuComponent* CuNetwork::ComponentFactory(std::istream& rIn) {
   else if (tag == "<blockarray>") pRet = new CuBlockArray(nInputs, nOutputs, pPred);
   // block-diagonal layer of band-split / hierarchical bottleneck networks (cuNetwork.cc:253, 285)
   else if (tag == "<discretelinearity>") pRet = new CuDiscreteLinearity(nInputs, nOutputs, pPred);
+  // masked, L1-regularised layer (cuNetwork.cc:255, 287)
+  else if (tag == "<sparselinearity>") pRet = new CuSparseLinearity(nInputs, nOutputs, pPred);
   // feature front end (cuNetwork.cc:263-268, cuCRBEDctFeat.h)
   else if (tag == "<expand>") pRet = new CuExpand(nInputs, nOutputs, pPred);
   else if (tag == "<copy>") pRet = new CuCopy(nInputs, nOutputs, pPred);

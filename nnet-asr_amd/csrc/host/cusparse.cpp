@@ -1,0 +1,157 @@
+// cusparse.cpp -- <sparselinearity> on the fused gfx950 update kernel.
+#include "cusparse.h"
+
+#include <cctype>
+
+#include "culayers.h"
+
+namespace TNet {
+
+#define S ((void*)CuDevice::Instantiate().Stream())
+
+void CuSparseLinearity::PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  CuProfileScope p("CuSparseLinearity::Propagate");
+  // Y = b + X W (AddScaledRow + Gemm('N','N'), cuSparseLinearity.cc:11-17) in one kernel: masked weights are zeros
+  KTScope kt("sparse_fwd:" + std::to_string(GetNInputs()) + "x" + std::to_string(GetNOutputs()),
+             2.0 * X.Rows() * GetNInputs() * GetNOutputs());
+  TNET_SAFE_CALL(tnet_affine_fwd(X.pCUData(), X.Dim(), mLinearity.pCUData(), mLinearity.Dim(), mBias.pCUData(),
+                                 Y.pCUData(), Y.Dim(), 0, S));
+}
+
+void CuSparseLinearity::BackpropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  CuProfileScope p("CuSparseLinearity::Backpropagate");
+  // Y = X W^T with beta 0 (Gemm('N','T'), cuSparseLinearity.cc:20-25)
+  KTScope kt("sparse_bwd:" + std::to_string(GetNInputs()) + "x" + std::to_string(GetNOutputs()),
+             2.0 * X.Rows() * GetNInputs() * GetNOutputs());
+  TNET_SAFE_CALL(tnet_affine_bwd(X.pCUData(), X.Dim(), mLinearity.pCUData(), mLinearity.Dim(), nullptr, 0,
+                                 Y.pCUData(), Y.Dim(), 0, S));
+}
+
+void CuSparseLinearity::UpdateConstants(size_t rows, float* scale, float* l1c, float* l2) const {
+  // cuSparseLinearity.cc:32-37, 50-58
+  BaseFloat N = 1;
+  if (mGradDivFrm) N = static_cast<BaseFloat>(rows);
+  BaseFloat mmt_gain = static_cast<BaseFloat>(1.0 / (1.0 - mMomentum));
+  N *= mmt_gain;
+  *scale = -mLearningRate / N;
+  const BaseFloat frm = mGradDivFrm ? 1.0f : (BaseFloat)rows;
+  *l1c = mL1Const > 0 ? mLearningRate * mL1Const * frm : 0.0f;
+  *l2 = mWeightcost > 0 ? -mLearningRate * mWeightcost * frm : 0.0f;
+}
+
+void CuSparseLinearity::Update() {
+  CuProfileScope p("CuSparseLinearity::Update");
+  const CuMatrix<BaseFloat>& X = GetInput();
+  const CuMatrix<BaseFloat>& E = GetErrorInput();
+  float scale, l1c, l2;
+  UpdateConstants(X.Rows(), &scale, &l1c, &l2);
+  {
+    // gradient, momentum, SGD, accu, mask, L1, L2 and the bias in one call
+    KTScope kt("sparse_upd:" + std::to_string(GetNInputs()) + "x" + std::to_string(GetNOutputs()),
+               2.0 * X.Rows() * GetNInputs() * GetNOutputs());
+    TNET_SAFE_CALL(tnet_sparse_update(
+        X.pCUData(), X.Dim(), E.pCUData(), E.Dim(), mLinearity.pCUData(), mLinearity.Dim(),
+        mLinearityCorrection.pCUData(), (int)mLinearityCorrection.Stride(), mLinearityCorrectionAccu.pCUData(),
+        (int)mLinearityCorrectionAccu.Stride(), (const unsigned*)mSparsityMask.pCUData(), (int)MaskStride(),
+        mBias.pCUData(), mBiasCorrection.pCUData(), scale, mMomentum, l1c, l2, S));
+  }
+  mNFrames += (long)X.Rows();
+}
+
+void CuSparseLinearity::UpdateMask() {
+  CuProfileScope p("CuSparseLinearity::UpdateMask");
+  TNET_SAFE_CALL(tnet_sparse_mask_update(mLinearity.pCUData(), mLinearity.Dim(), (unsigned*)mSparsityMask.pCUData(),
+                                         (int)MaskStride(), mLinearityCorrectionAccu.pCUData(),
+                                         (int)mLinearityCorrectionAccu.Stride(), mSparsifyWeightThreshold,
+                                         mUnsparsifyAccu, (BaseFloat)mNFrames, S));
+}
+
+void CuSparseLinearity::GetMask(BaseFloat* mask, size_t ld) const {
+  CuMatrix<BaseFloat> tmp(mLinearity.Rows(), mLinearity.Cols());
+  TNET_SAFE_CALL(tnet_sparse_mask_unpack((const unsigned*)mSparsityMask.pCUData(), (int)MaskStride(), tmp.pCUData(),
+                                         tmp.Dim(), S));
+  tmp.CopyToHost(mask, ld);
+}
+
+void CuSparseLinearity::SetMask(const BaseFloat* mask, size_t ld) {
+  CuMatrix<BaseFloat> tmp;
+  tmp.CopyFromHost(mask, mLinearity.Rows(), mLinearity.Cols(), ld);
+  mSparsityMask.Init(mLinearity.Rows() * MaskStride());
+  TNET_SAFE_CALL(tnet_sparse_mask_pack(tmp.pCUData(), tmp.Dim(), (unsigned*)mSparsityMask.pCUData(), (int)MaskStride(),
+                                       S));
+  CuDevice::Instantiate().Synchronize();  // tmp goes away
+}
+
+// the next non-blank character, left in the stream (no state flag set at the end of the file)
+static int PeekNonSpace(std::istream& in) {
+  std::streambuf* sb = in.rdbuf();
+  int c = sb->sgetc();
+  while (c != EOF && std::isspace(c)) c = sb->snextc();
+  return c;
+}
+
+void CuSparseLinearity::ReadFromStream(std::istream& rIn) {
+  // matrix stored transposed as SNet does, then the bias (cuSparseLinearity.cc:100-111)
+  BfMatrix transpose;
+  ReadMatrixFast(rIn, transpose);
+  BfVector bias;
+  ReadVectorFast(rIn, bias);
+  // optional sparsity mask, transposed like the matrix; without one every weight is active (.cc:113-126)
+  BfMatrix mask_transp;
+  const bool have_mask = PeekNonSpace(rIn) == 'm';
+  if (have_mask) ReadMatrixFast(rIn, mask_transp);
+  // optional matrix of accumulated gradients: read and dropped (.cc:128-133)
+  if (PeekNonSpace(rIn) == 'm') {
+    BfMatrix dummy;
+    ReadMatrixFast(rIn, dummy);
+  }
+  if (transpose.Cols() * transpose.Rows() == 0) Error("Missing linearity matrix in network file");
+  if (bias.Dim() == 0) Error("Missing bias vector in network file");
+  if (transpose.Rows() != GetNOutputs() || transpose.Cols() != GetNInputs() || bias.Dim() != GetNOutputs()) {
+    std::ostringstream os;
+    os << "Wrong dimensionalities of matrix/vector in network file\n"
+       << "Inputs:" << GetNInputs() << "Outputs:" << GetNOutputs() << "\n"
+       << "linearityCols:" << transpose.Rows() << "linearityRows:" << transpose.Cols() << "biasDims:" << bias.Dim()
+       << "\n";
+    Error(os.str());
+  }
+  if (have_mask && (mask_transp.Rows() != transpose.Rows() || mask_transp.Cols() != transpose.Cols())) {
+    std::ostringstream os;
+    os << "Wrong dimensionality of the sparsity mask in network file\n"
+       << "maskCols:" << mask_transp.Rows() << "maskRows:" << mask_transp.Cols() << "\n";
+    Error(os.str());
+  }
+  mLinearity.CopyFrom(BfMatrix(transpose, TRANS));
+  mBias.CopyFrom(bias);
+  // the mask is not applied to W here, only by updates, as in the reference
+  BfMatrix mask(transpose.Cols(), transpose.Rows());
+  for (size_t r = 0; r < mask.Rows(); r++)
+    for (size_t c = 0; c < mask.Cols(); c++) mask(r, c) = have_mask ? mask_transp(c, r) : 1.0f;
+  SetMask(mask.pData(), mask.Stride());
+  // momentum buffers, the accumulator and the frame count start at zero
+  mLinearityCorrection.Init(mLinearity.Rows(), mLinearity.Cols());
+  mLinearityCorrection.SetZero();
+  mBiasCorrection.Init(mBias.Dim());
+  mBiasCorrection.SetZero();
+  mLinearityCorrectionAccu.Init(mLinearity.Rows(), mLinearity.Cols());
+  mLinearityCorrectionAccu.SetZero();
+  mNFrames = 0;
+}
+
+void CuSparseLinearity::WriteToStream(std::ostream& rOut) {
+  UpdateMask();
+  // cuSparseLinearity.cc:169-185
+  BfMatrix tmp;
+  mLinearity.CopyTo(tmp);
+  rOut << BfMatrix(tmp, TRANS);
+  BfVector vec;
+  mBias.CopyTo(vec);
+  rOut << vec;
+  rOut << std::endl;
+  GetMask(tmp.pData(), tmp.Stride());
+  rOut << BfMatrix(tmp, TRANS);
+  mLinearityCorrectionAccu.CopyTo(tmp);
+  rOut << BfMatrix(tmp, TRANS);
+}
+
+}  // namespace TNet

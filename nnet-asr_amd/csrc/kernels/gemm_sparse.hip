@@ -1,0 +1,333 @@
+// gemm_sparse.hip -- the weight update and the mask kernels of <sparselinearity>
+// (src/CuTNetLib/cuSparseLinearity.cc:28-97, cukernels.cu:34-62).
+//
+// The layer is a dense affine transform whose weights carry a 0/1 sparsity mask: forward and backward are the
+// library's dense GEMMs (W holds exact zeros under the mask); only the update differs.  The reference's Update is a
+// GEMM followed by five element-wise passes over [n_in x n_out] matrices (AddScaled, the accu AddScaled, ApplyMask,
+// ApplyL1, the L2 AddScaled); here the whole tail is per-element arithmetic applied to the gradient tile:
+//   c = g + mmt*corrW ; corrW = c ; w = W + scale*c ; accu += c ; w = 0 where the mask is 0 ;
+//   l1c > 0: w = |w| < l1c ? 0 : (w > 0 ? w - l1c : w + l1c) ; l2 != 0: w = w + l2*w ; W = w
+// in one of two forms:
+//   single launch  the unsplit X^T E tile stays in the MFMA accumulators of gemm_tile.h's tile core and the
+//                  epilogue applies the arithmetic in place; the first tile-row's workgroups also sum the columns
+//                  of E (fp32 inside a 32-row slab, fp64 across slabs) and update the bias.  For layers whose tile
+//                  grid alone fills the GPU.
+//   sliced         `rows` is cut into K slices whose partial products go to the per-stream workspace; a second
+//                  launch adds them in slice order and applies the same arithmetic (tnet_shared_update's scheme).
+//                  For small layers.
+// Neither form uses atomics: the same inputs give the same bits.
+//
+// The mask is a bit matrix on the device: row r has ceil(n_out / 32) uint32 words at a word stride ldmask, bit
+// c & 31 of word c >> 5 is the mask of W[r][c], bits at columns >= n_out are zero.  In the tile core's fragment
+// layout a lane's T values of one output row lie 16 columns apart from a column origin that is a multiple of 32,
+// so one mask word serves two of them: the epilogue loads a word once per row and 32 columns.
+#include "gemm_tile.h"
+
+#include <algorithm>
+
+namespace tnetk {
+namespace {
+
+struct SparseArgs {
+  float* W; long ldw;
+  float* corr; long ldcorr;
+  float* accu; long ldaccu;
+  const unsigned* bits; long ldmask;
+  float* b;
+  float* corr_b;
+  float scale, mmt, l1c, l2;
+};
+
+// steps 2, 4 and 6-9 of the update for one element whose gradient is g and whose mask bit is m
+__device__ __forceinline__ void sparse_apply(const SparseArgs& s, int row, int col, float g, unsigned m) {
+  float* qc = s.corr + (long)row * s.ldcorr + col;
+  float* qa = s.accu + (long)row * s.ldaccu + col;
+  float* qw = s.W + (long)row * s.ldw + col;
+  const float c = g + s.mmt * *qc;
+  *qc = c;
+  float w = *qw + s.scale * c;
+  *qa = *qa + c;
+  if (!m) w = 0.f;
+  if (s.l1c > 0.f) w = (fabsf(w) < s.l1c) ? 0.f : (w > 0.f ? w - s.l1c : w + s.l1c);
+  if (s.l2 != 0.f) w = w + s.l2 * w;
+  *qw = w;
+}
+
+__device__ __forceinline__ void sparse_apply_bias(const SparseArgs& s, int col, double sum) {
+  float g = (float)sum;
+  g = g + s.mmt * s.corr_b[col];
+  s.corr_b[col] = g;
+  s.b[col] = s.b[col] + s.scale * g;
+}
+
+// the single-launch form's epilogue (gemm_tile.h EPI)
+struct SparseEpi {
+  SparseArgs s;
+  template <int T>
+  __device__ __forceinline__ void row(const TileWork& w, int row, int c0, int l15, const float (&v)[T]) const {
+#pragma unroll
+    for (int j = 0; j < T / 2; ++j) {
+      const int cw = c0 + 32 * j;  // a multiple of 32: columns cw .. cw + 31 are one mask word
+      if (cw >= w.N) break;
+      const unsigned word = s.bits[(long)row * s.ldmask + (cw >> 5)];
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const int col = cw + 16 * h + l15;
+        if (col < w.N) sparse_apply(s, row, col, v[2 * j + h], (word >> (16 * h + l15)) & 1u);
+      }
+    }
+  }
+  __device__ __forceinline__ void colsum(const TileWork&, int col, double sum) const {
+    sparse_apply_bias(s, col, sum);
+  }
+};
+
+struct SparseP {
+  const float* X; long ldx;
+  const float* E; long lde;
+  int M, N, K;                 // n_in, n_out, rows
+  int tn, tiles;               // tile columns, tiles of the [M x N] grid
+  int vecX, vecE;              // 16-byte loads allowed
+  int kchunk;                  // sliced: rows per K slice (a multiple of kSlab)
+  float* part; long ldp, pslab;  // sliced: partial products [kslices][M][ldp]
+  double* bpart;               // sliced: partial column sums of E [kslices][N]
+  SparseArgs s;
+};
+
+template <int T, bool FUSED>
+__global__ __launch_bounds__(kThreads) void sparse_gemm_kernel(const SparseP p) {
+  constexpr int BT = 32 * T;
+  const int z = (int)blockIdx.x / p.tiles, rem = (int)blockIdx.x % p.tiles;  // z: the K slice (0 when fused)
+  const long krow0 = FUSED ? 0 : (long)z * p.kchunk;
+  TileWork w;
+  w.A = p.X + krow0 * p.ldx; w.lda = p.ldx;  // A[m][k] = X[k][m]: m contiguous
+  w.B = p.E + krow0 * p.lde; w.ldb = p.lde;
+  w.M = p.M; w.N = p.N; w.K = FUSED ? p.K : min(p.kchunk, p.K - (int)krow0);
+  w.bm = (rem / p.tn) * BT; w.bn = (rem % p.tn) * BT;
+  w.vecA = p.vecX; w.vecB = p.vecE;
+  w.C = nullptr; w.ldc = 0; w.bias = nullptr;
+  if (FUSED) {
+    w.P = nullptr; w.ldp = 0; w.bp = nullptr;
+    tile_gemm<MODE_UPD, T, 1, SparseEpi>(w, SparseEpi{p.s});
+  } else {
+    w.P = p.part + (long)z * p.pslab; w.ldp = p.ldp;
+    w.bp = p.bpart + (long)z * p.N;
+    tile_gemm<MODE_UPD, T>(w);
+  }
+}
+
+// The sliced form's second launch.  Element (row, col) of W: the slices' partial products added in slice order,
+// then sparse_apply.  The last N threads: the bias, its gradient the slices' column sums added in fp64 in the
+// same order.
+__global__ __launch_bounds__(kThreads) void sparse_combine_kernel(const float* __restrict__ P, long pslab, long ldp,
+                                                                  const double* __restrict__ bpart, int Z, int M, int N,
+                                                                  const SparseArgs s) {
+  const long idx = (long)blockIdx.x * kThreads + threadIdx.x, nw = (long)M * N;
+  if (idx < nw) {
+    const int row = (int)(idx / N), col = (int)(idx % N);
+    const float* q = P + (long)row * ldp + col;
+    float g = q[0];
+    for (int z = 1; z < Z; ++z) g += q[(long)z * pslab];
+    const unsigned word = s.bits[(long)row * s.ldmask + (col >> 5)];
+    sparse_apply(s, row, col, g, (word >> (col & 31)) & 1u);
+  } else if (idx < nw + N) {
+    const int col = (int)(idx - nw);
+    double sum = 0.0;
+    for (int z = 0; z < Z; ++z) sum += bpart[(long)z * N + col];
+    sparse_apply_bias(s, col, sum);
+  }
+}
+
+// ---- mask kernels: one thread per element, 256 consecutive columns of one row per workgroup; a wavefront's
+// ballot is two mask words, stored by lanes 0 and 32 -- a word has one writer
+__device__ __forceinline__ void store_ballot(bool bit, unsigned* __restrict__ row_words, int col, int nwords) {
+  const unsigned long long bal = __ballot(bit);
+  const int lane = (int)threadIdx.x & 63, word = col >> 5;
+  if ((lane & 31) == 0 && word < nwords) row_words[word] = (unsigned)(bal >> lane);
+}
+
+__global__ __launch_bounds__(kThreads) void mask_pack_kernel(const float* __restrict__ maskf, int cols, long ldf,
+                                                             unsigned* __restrict__ bits, long ldmask, int cblocks) {
+  const int row = (int)(blockIdx.x / cblocks), col = (int)(blockIdx.x % cblocks) * kThreads + (int)threadIdx.x;
+  const bool bit = col < cols && maskf[(long)row * ldf + col] != 0.f;
+  store_ballot(bit, bits + (long)row * ldmask, col, (cols + 31) >> 5);
+}
+
+__global__ __launch_bounds__(kThreads) void mask_unpack_kernel(const unsigned* __restrict__ bits, long ldmask,
+                                                               int cols, float* __restrict__ maskf, long ldf,
+                                                               int cblocks) {
+  const int row = (int)(blockIdx.x / cblocks), col = (int)(blockIdx.x % cblocks) * kThreads + (int)threadIdx.x;
+  if (col < cols) maskf[(long)row * ldf + col] = (float)((bits[(long)row * ldmask + (col >> 5)] >> (col & 31)) & 1u);
+}
+
+// CuSparseLinearity::UpdateMask (cuSparseLinearity.cc:66-97) on the device
+__global__ __launch_bounds__(kThreads) void mask_update_kernel(float* __restrict__ W, int cols, long ldw,
+                                                               unsigned* __restrict__ bits, long ldmask,
+                                                               const float* __restrict__ accu, long ldaccu,
+                                                               float sparsify, float unsparsify, float nframes,
+                                                               int cblocks) {
+  const int row = (int)(blockIdx.x / cblocks), col = (int)(blockIdx.x % cblocks) * kThreads + (int)threadIdx.x;
+  bool bit = false;
+  if (col < cols) {
+    bit = (bits[(long)row * ldmask + (col >> 5)] >> (col & 31)) & 1u;
+    if (bit) {  // active: cut a weight below the threshold
+      float* q = W + (long)row * ldw + col;
+      if (fabsf(*q) < sparsify) {
+        bit = false;
+        *q = 0.f;
+      }
+    } else if (fabsf(accu[(long)row * ldaccu + col]) / nframes > unsparsify) {  // inactive: W stays as it is
+      bit = true;
+    }
+  }
+  // (every lane of the wavefront reads its old word before any lane stores: the ballot waits for all of them)
+  store_ballot(bit, bits + (long)row * ldmask, col, (cols + 31) >> 5);
+}
+
+// Form and tile choice (measured, tools/sparse_bench.py / profiles/sparse_linearity.json): see the routing note in
+// tnet_sparse_update below.
+constexpr int kFormMask = 0xF, kForce128 = 0x20;
+// Single launch from 512 tiles of 64x64 on (two workgroups per CU).  Measured medians, bunch 1024 / 256, single
+// launch against sliced: 2048x2048 (1024 tiles) 96 / 39 us against 105 / 46; 1024x2048 (512 tiles) 67 / 28 against
+// 71 / 31; 440x2048 (224 tiles) 54 / 20 against 36 / 20; 1024x135 (48 tiles) 58 / 19 against 18 / 11.  Below the
+// threshold the unsplit K leaves a CU with one workgroup whose loads nothing hides.  The chain of older entry points
+// (tnet_affine_update + five element-wise launches) is slower than the chosen form in every cell (1.08x - 3.5x), so
+// nothing is routed to it.
+constexpr long kSingleMinTiles64 = 512;
+int g_form = 0;
+
+bool mask_args_ok(const void* bits, int ldmask, int cols) { return bits && aligned4(bits) && ldmask >= cdiv(cols, 32); }
+size_t mask_bytes(int rows, int ldmask) { return (size_t)std::max(rows, 0) * (size_t)ldmask * 4; }
+size_t mat_bytes(TnetMatrixDim d) { return (size_t)std::max(d.rows, 0) * (size_t)d.stride * 4; }
+
+}  // namespace
+}  // namespace tnetk
+
+using namespace tnetk;
+
+extern "C" int tnet_sparse_update_form(int form) {
+  const int was = g_form;
+  g_form = form;
+  return was;
+}
+
+extern "C" int tnet_sparse_mask_pack(const float* maskf, TnetMatrixDim d, unsigned* bits, int ldmask, void* stream) {
+  if (!dim_ok(maskf, d) || !mask_args_ok(bits, ldmask, d.cols) ||
+      overlap_bytes(maskf, mat_bytes(d), bits, mask_bytes(d.rows, ldmask)))
+    return TNET_ERR_ARG;
+  if (d.rows == 0) return TNET_OK;
+  const int cb = cdiv(d.cols, kThreads);
+  const long grid = (long)d.rows * cb;
+  if (grid > 0x7fffffffL) return TNET_ERR_ARG;
+  mask_pack_kernel<<<(unsigned)grid, kThreads, 0, (hipStream_t)stream>>>(maskf, d.cols, d.stride, bits, ldmask, cb);
+  TNET_LAUNCH_CHECK();
+  return TNET_OK;
+}
+
+extern "C" int tnet_sparse_mask_unpack(const unsigned* bits, int ldmask, float* maskf, TnetMatrixDim d, void* stream) {
+  if (!dim_ok(maskf, d) || !mask_args_ok(bits, ldmask, d.cols) ||
+      overlap_bytes(maskf, mat_bytes(d), bits, mask_bytes(d.rows, ldmask)))
+    return TNET_ERR_ARG;
+  if (d.rows == 0) return TNET_OK;
+  const int cb = cdiv(d.cols, kThreads);
+  const long grid = (long)d.rows * cb;
+  if (grid > 0x7fffffffL) return TNET_ERR_ARG;
+  mask_unpack_kernel<<<(unsigned)grid, kThreads, 0, (hipStream_t)stream>>>(bits, ldmask, d.cols, maskf, d.stride, cb);
+  TNET_LAUNCH_CHECK();
+  return TNET_OK;
+}
+
+extern "C" int tnet_sparse_mask_update(float* W, TnetMatrixDim dW, unsigned* bits, int ldmask, const float* accu,
+                                       int ldaccu, float sparsify_threshold, float unsparsify_accu, float nframes,
+                                       void* stream) {
+  if (!dim_ok(W, dW) || !mask_args_ok(bits, ldmask, dW.cols) || !accu || !aligned4(accu) || ldaccu < dW.cols ||
+      (ldaccu & 3))
+    return TNET_ERR_ARG;
+  const TnetMatrixDim dA{dW.rows, dW.cols, ldaccu};
+  if (overlap(W, dW, accu, dA) || overlap_bytes(W, mat_bytes(dW), bits, mask_bytes(dW.rows, ldmask)) ||
+      overlap_bytes(accu, mat_bytes(dA), bits, mask_bytes(dW.rows, ldmask)))
+    return TNET_ERR_ARG;
+  if (dW.rows == 0) return TNET_OK;
+  const int cb = cdiv(dW.cols, kThreads);
+  const long grid = (long)dW.rows * cb;
+  if (grid > 0x7fffffffL) return TNET_ERR_ARG;
+  mask_update_kernel<<<(unsigned)grid, kThreads, 0, (hipStream_t)stream>>>(
+      W, dW.cols, dW.stride, bits, ldmask, accu, ldaccu, sparsify_threshold, unsparsify_accu, nframes, cb);
+  TNET_LAUNCH_CHECK();
+  return TNET_OK;
+}
+
+extern "C" int tnet_sparse_update(const float* X, TnetMatrixDim dX, const float* E, TnetMatrixDim dE, float* W,
+                                  TnetMatrixDim dW, float* corrW, int ldcorr, float* accu, int ldaccu,
+                                  const unsigned* bits, int ldmask, float* b, float* corr_b, float scale, float mmt,
+                                  float l1c, float l2, void* stream) {
+  if (!dim_ok(X, dX) || !dim_ok(E, dE) || !dim_ok(W, dW) || dW.rows < 1 || !b || !aligned4(b) || !corr_b ||
+      !aligned4(corr_b) || dX.cols != dW.rows || dE.cols != dW.cols || dX.rows != dE.rows)
+    return TNET_ERR_ARG;
+  if (!corrW || !aligned4(corrW) || ldcorr < dW.cols || (ldcorr & 3) || !accu || !aligned4(accu) ||
+      ldaccu < dW.cols || (ldaccu & 3) || !mask_args_ok(bits, ldmask, dW.cols))
+    return TNET_ERR_ARG;
+  {  // no parameter buffer on an activation, no two parameter buffers on each other
+    const void* q[4] = {W, corrW, accu, bits};
+    const size_t n[4] = {mat_bytes(dW), mat_bytes(TnetMatrixDim{dW.rows, dW.cols, ldcorr}),
+                         mat_bytes(TnetMatrixDim{dW.rows, dW.cols, ldaccu}), mask_bytes(dW.rows, ldmask)};
+    for (int i = 0; i < 4; ++i) {
+      if (overlap_bytes(q[i], n[i], X, mat_bytes(dX)) || overlap_bytes(q[i], n[i], E, mat_bytes(dE)))
+        return TNET_ERR_ARG;
+      for (int j = i + 1; j < 4; ++j)
+        if (overlap_bytes(q[i], n[i], q[j], n[j])) return TNET_ERR_ARG;
+    }
+  }
+  hipStream_t st = (hipStream_t)stream;
+  const int rows = dX.rows;
+  SparseP p{};
+  p.X = X; p.ldx = dX.stride;
+  p.E = E; p.lde = dE.stride;
+  p.M = dW.rows; p.N = dW.cols; p.K = rows;
+  p.vecX = aligned16(X); p.vecE = aligned16(E);
+  p.s = SparseArgs{W, dW.stride, corrW, ldcorr, accu, ldaccu, bits, ldmask, b, corr_b, scale, mmt, l1c, l2};
+
+  // Routing (measured, tools/sparse_bench.py / profiles/sparse_linearity.json).  64x64 tiles in both forms: the
+  // 128x128 tile lost in every measured cell (2048x2048, bunch 1024: 134 us against 96 us single launch, a grid of
+  // 256 workgroups of one wavefront per SIMD cannot hide the epilogue's read-modify-write of three matrices); it is
+  // kept behind the form knob so that the measurement can be repeated.  Single launch from kSingleMinTiles64
+  // 64x64 tiles on, sliced below: see the constant.
+  const long tiles64 = (long)cdiv(p.M, 64) * cdiv(p.N, 64), tiles128 = (long)cdiv(p.M, 128) * cdiv(p.N, 128);
+  const int form = g_form & kFormMask;
+  const bool single = form == 1 || (form == 0 && tiles64 >= kSingleMinTiles64);
+  const int T = (g_form & kForce128) ? 4 : 2;
+  p.tn = cdiv(p.N, 32 * T);
+  if ((T == 4 ? tiles128 : tiles64) > 0x7fffffffL) return TNET_ERR_ARG;
+  p.tiles = cdiv(p.M, 32 * T) * p.tn;
+
+  if (single) {
+    // rows == 0: K = 0, the accumulators stay zero and the epilogue still applies momentum, mask, L1 and L2
+    if (T == 4) sparse_gemm_kernel<4, true><<<(unsigned)p.tiles, kThreads, 0, st>>>(p);
+    else sparse_gemm_kernel<2, true><<<(unsigned)p.tiles, kThreads, 0, st>>>(p);
+    TNET_LAUNCH_CHECK();
+    return TNET_OK;
+  }
+  // K slices: rows cut (in multiples of the 32-row slab) until about two workgroups per CU are in flight
+  // (tnet_shared_update's rule)
+  int want = (int)std::min<long>(cdiv(512, p.tiles), 64);
+  want = std::max(1, std::min(want, cdiv(std::max(rows, 1), kSlab)));
+  p.kchunk = cdiv(cdiv(std::max(rows, 1), want), kSlab) * kSlab;
+  const int Z = cdiv(std::max(rows, 1), p.kchunk);
+  p.ldp = (p.N + 3) & ~3L;
+  p.pslab = (long)p.M * p.ldp;
+  const long grid = (long)p.tiles * Z;
+  if (grid > 0x7fffffffL) return TNET_ERR_ARG;
+  const size_t bbytes = (((size_t)Z * p.N * sizeof(double)) + 255) & ~(size_t)255;
+  char* ws = (char*)tile_workspace(bbytes + (size_t)Z * p.pslab * sizeof(float), st);
+  if (!ws) return TNET_ERR_RUNTIME;
+  p.bpart = (double*)ws;
+  p.part = (float*)(ws + bbytes);
+  if (T == 4) sparse_gemm_kernel<4, false><<<(unsigned)grid, kThreads, 0, st>>>(p);
+  else sparse_gemm_kernel<2, false><<<(unsigned)grid, kThreads, 0, st>>>(p);
+  TNET_LAUNCH_CHECK();
+  const long n = (long)p.M * p.N + p.N;
+  sparse_combine_kernel<<<(unsigned)cdiv(n, kThreads), kThreads, 0, st>>>(p.part, p.pslab, p.ldp, p.bpart, Z, p.M, p.N,
+                                                                          p.s);
+  TNET_LAUNCH_CHECK();
+  return TNET_OK;
+}

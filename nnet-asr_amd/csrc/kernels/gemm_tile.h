@@ -1,5 +1,6 @@
 // gemm_tile.h -- the fp32 MFMA tile core shared by the instance-batched (gemm_shared.hip) and the grouped
-// (gemm_discrete.hip) GEMM kernels.  A kernel works out, from blockIdx, which operand windows and which output
+// (gemm_discrete.hip) GEMM kernels and by the <sparselinearity> update (gemm_sparse.hip, which hooks its own
+// epilogue into the update mode).  A kernel works out, from blockIdx, which operand windows and which output
 // tile its workgroup owns (TileWork) and calls tile_gemm: 256 threads = 2 x 2 waves on
 // v_mfma_f32_16x16x4_f32 (fp32 in / fp32 accumulate), a 64x64 or 128x128 output tile, k-tiles of 16 staged
 // through a double-buffered LDS image [k][m or n] (row pitch tile + 16 floats: the four k rows a wave's MFMA
@@ -103,8 +104,24 @@ __device__ __forceinline__ void store_tile(float* __restrict__ s, const f32x4 (&
 // PF: k-tiles whose global loads are in flight while one is multiplied (register stages; the LDS image stays
 // double-buffered).  1 hides a load behind one k-tile's MFMAs, which is enough where several workgroups share a
 // CU; 2 is for grids of few workgroups with deep K, where one k-tile's work is shorter than the load latency.
-template <int MODE, int T, int PF = 1>
-__device__ __forceinline__ void tile_gemm(const TileWork& w) {
+// EPI (update only): what becomes of the finished tile.  row(w, row, c0, l15, v): the lane's T values of output row
+// `row`, v[b] the element at column c0 + 16 * b + l15 (c0 a multiple of 32; row < w.M checked, the columns are
+// not); colsum(w, col, s): column col's sum of B over the K rows (first tile-row's workgroups, col < w.N checked).
+// StorePartial writes both to the slice's partial buffers; gemm_sparse.hip applies its update in place instead.
+struct StorePartial {
+  template <int T>
+  __device__ __forceinline__ void row(const TileWork& w, int row, int c0, int l15, const float (&v)[T]) const {
+#pragma unroll
+    for (int b = 0; b < T; ++b) {
+      const int col = c0 + b * 16 + l15;
+      if (col < w.N) w.P[(long)row * w.ldp + col] = v[b];
+    }
+  }
+  __device__ __forceinline__ void colsum(const TileWork& w, int col, double s) const { w.bp[col] = s; }
+};
+
+template <int MODE, int T, int PF = 1, class EPI = StorePartial>
+__device__ __forceinline__ void tile_gemm(const TileWork& w, const EPI epi = EPI()) {
   static_assert(PF == 1 || PF == 2, "the LDS buffer index below assumes PF divides 2");
   constexpr int BT = 32 * T;     // workgroup tile edge
   constexpr int S = BT + 16;     // LDS row pitch
@@ -192,23 +209,21 @@ __device__ __forceinline__ void tile_gemm(const TileWork& w) {
 
   // epilogue: accumulator register r of MFMA tile (a, b) is row 4 * (lane >> 4) + r, column lane & 15
   if (MODE == MODE_UPD) {
-    float* P = w.P;
 #pragma unroll
     for (int a = 0; a < T; ++a)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = bm + wm + a * 16 + lk * 4 + r;
         if (row >= w.M) continue;
+        float v[T];
 #pragma unroll
-        for (int b = 0; b < T; ++b) {
-          const int col = bn + wn + b * 16 + l15;
-          if (col < w.N) P[(long)row * w.ldp + col] = acc[a][b][r];
-        }
+        for (int b = 0; b < T; ++b) v[b] = acc[a][b][r];
+        epi.template row<T>(w, row, bn + wn, l15, v);
       }
     if (colsum) {
       cd += (double)cs;
       const int col = bn + (int)threadIdx.x;
-      if (col < w.N) w.bp[col] = cd;
+      if (col < w.N) epi.colsum(w, col, cd);
     }
   } else {
     float* C = w.C;

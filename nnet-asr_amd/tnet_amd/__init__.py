@@ -301,6 +301,42 @@ class Network:
                 raise ValueError("set_discrete_params: shape mismatch")
             check(lib().tnet_net_discrete_set(self.h, i, 0, None, b.ctypes.data), "discrete_set")
 
+    def set_l1(self, l1: float) -> None:
+        """CuNetwork::SetL1 (TNetCu --L1): the L1 constant of every <sparselinearity> component."""
+        check(lib().tnet_net_set_l1(self.h, l1), "set_l1")
+
+    def sparse_params(self, i: int = 0):
+        """(W [n_in x n_out], bias [n_out], mask (0/1 floats), accu, nframes) of a <sparselinearity> component."""
+        check(lib().tnet_net_sparse_get(self.h, i, None, None, None, None, None), "sparse_get")  # index and type
+        _, ni, no = self.components()[i]
+        W, mask, accu = (np.empty((ni, no), np.float32) for _ in range(3))
+        b = np.empty(no, np.float32)
+        n = C.c_long()
+        check(lib().tnet_net_sparse_get(self.h, i, W.ctypes.data, b.ctypes.data, mask.ctypes.data, accu.ctypes.data,
+                                        C.byref(n)), "sparse_get")
+        return W, b, mask, accu, n.value
+
+    def set_sparse_params(self, i: int, W=None, b=None, mask=None) -> None:
+        """Any of W, b, mask (nonzero -> active); setting the mask does not touch W."""
+        check(lib().tnet_net_sparse_get(self.h, i, None, None, None, None, None), "sparse_get")
+        _, ni, no = self.components()[i]
+        args = []
+        for a, shape in ((W, (ni, no)), (b, (no,)), (mask, (ni, no))):
+            a = None if a is None else np.ascontiguousarray(a, np.float32)
+            if a is not None and a.shape != shape:
+                raise ValueError("set_sparse_params: shape mismatch")
+            args.append(a)
+        check(lib().tnet_net_sparse_set(self.h, i, *(None if a is None else a.ctypes.data for a in args)),
+              "sparse_set")
+
+    def set_sparse_thresholds(self, i: int, sparsify_threshold: float = -1.0, unsparsify_accu: float = -1.0) -> None:
+        """The thresholds of CuSparseLinearity::UpdateMask; a negative value leaves one as it is."""
+        check(lib().tnet_net_sparse_thresholds(self.h, i, sparsify_threshold, unsparsify_accu), "sparse_thresholds")
+
+    def sparse_update_mask(self, i: int = 0) -> None:
+        """CuSparseLinearity::UpdateMask now (it also runs at the start of every write())."""
+        check(lib().tnet_net_sparse_update_mask(self.h, i), "sparse_update_mask")
+
     def rbm_params(self, i: int = 0):
         """(W [n_vis x n_hid], vis_bias, hid_bias, (vis_type, hid_type)) of an <rbm> component."""
         _, ni, no = self.components()[i]

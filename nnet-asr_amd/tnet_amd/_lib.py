@@ -121,6 +121,12 @@ _SIGS = {
     "tnet_discrete_fwd": (i32, [vp, MatrixDim, vp, vp, vp, vp, MatrixDim, vp]),
     "tnet_discrete_bwd": (i32, [vp, MatrixDim, vp, vp, vp, MatrixDim, vp]),
     "tnet_discrete_update": (i32, [vp, MatrixDim, vp, MatrixDim, vp, vp, vp, vp, vp, f32, f32, f32, vp]),
+    "tnet_sparse_mask_pack": (i32, [vp, MatrixDim, vp, i32, vp]),
+    "tnet_sparse_mask_unpack": (i32, [vp, i32, vp, MatrixDim, vp]),
+    "tnet_sparse_update": (i32, [vp, MatrixDim, vp, MatrixDim, vp, MatrixDim, vp, i32, vp, i32, vp, i32, vp, vp, f32,
+                                 f32, f32, f32, vp]),
+    "tnet_sparse_update_form": (i32, [i32]),
+    "tnet_sparse_mask_update": (i32, [vp, MatrixDim, vp, i32, vp, i32, f32, f32, f32, vp]),
     "tnet_sgd_update": (i32, [vp, vp, vp, i64, f32, f32, f32, vp]),
     "tnet_bias_update": (i32, [vp, MatrixDim, vp, vp, vp, f32, f32, vp, vp]),
     "tnet_softmax_xent": (i32, [vp, MatrixDim, vp, vp, i32, vp, i32, vp, vp]),
@@ -225,6 +231,11 @@ _SIGS = {
     "tnet_net_discrete_blocks": (i32, [vp, i32, vp, vp, vp]),
     "tnet_net_discrete_get": (i32, [vp, i32, i32, vp, vp]),
     "tnet_net_discrete_set": (i32, [vp, i32, i32, vp, vp]),
+    "tnet_net_set_l1": (i32, [vp, f32]),
+    "tnet_net_sparse_get": (i32, [vp, i32, vp, vp, vp, vp, C.POINTER(i64)]),
+    "tnet_net_sparse_set": (i32, [vp, i32, vp, vp, vp]),
+    "tnet_net_sparse_thresholds": (i32, [vp, i32, f32, f32]),
+    "tnet_net_sparse_update_mask": (i32, [vp, i32]),
     "tnet_rnn_trainer_create": (vp, [vp, vp, i32, i32]),
     "tnet_rnn_trainer_free": (i32, [vp]),
     "tnet_rnn_trainer_utterance": (i32, [vp, vp, i32, i32, i32, vp]),

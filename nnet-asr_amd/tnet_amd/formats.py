@@ -90,6 +90,20 @@ def _write_layers(out, layers: Sequence[Layer], precision: int) -> None:
             b = np.asarray(L.b, dtype=np.float32)
             out.write(f"v {b.shape[0]}  " + " ".join(_fmt(v, precision) for v in b) + " ")
             out.write("\n\n")
+        elif L.tag == "<sparselinearity>":       # cuSparseLinearity.cc:163-186: W^T, bias, then mask^T and accu^T
+            mats = [L.W] + [L.extra[k] for k in ("mask", "accu") if L.extra.get(k) is not None]
+            if "accu" in L.extra and L.extra.get("mask") is None:
+                raise ValueError("<sparselinearity>: an accu matrix needs a mask matrix before it")
+            for k, M in enumerate(mats):
+                Mt = np.asarray(M, dtype=np.float32).T
+                out.write(f"m {Mt.shape[0]} {Mt.shape[1]}\n")
+                for row in Mt:
+                    out.write(" ".join(_fmt(v, precision) for v in row))
+                    out.write(" \n")
+                if k == 0:
+                    b = np.asarray(L.b, dtype=np.float32)
+                    out.write(f"v {b.shape[0]}  " + " ".join(_fmt(v, precision) for v in b) + " ")
+                    out.write("\n\n")
         elif L.tag == "<blockarray>":            # cuBlockArray.cc:125-135
             blocks = L.extra["blocks"]
             out.write(f" {len(blocks)} ")
@@ -209,6 +223,28 @@ def read_nnet(path_or_text: str) -> List[Layer]:
                         or L.b.shape[0] != n_out):
                     raise ValueError("Wrong dimensionalities of matrix/vector in network file")
                 L.extra["Ws"] = Ws
+            elif tag == "<sparselinearity>":
+                # cuSparseLinearity.cc:100-160: W^T, bias, then an optional mask^T and an optional accu^T (which
+                # the library reads and drops); a mask of another shape than W is an error here too
+                if i >= len(toks) or toks[i] != "m":
+                    raise ValueError("Missing linearity matrix in network file")
+                L.W = np.ascontiguousarray(read_matrix().T)
+                if i >= len(toks) or toks[i] != "v":
+                    raise ValueError("Missing bias vector in network file")
+                L.b = read_vector()
+                if L.W.size == 0:
+                    raise ValueError("Missing linearity matrix in network file")
+                if L.b.size == 0:
+                    raise ValueError("Missing bias vector in network file")
+                if L.W.shape != (n_in, n_out) or L.b.shape != (n_out,):
+                    raise ValueError("Wrong dimensionalities of matrix/vector in network file")
+                if i < len(toks) and toks[i] == "m":
+                    L.extra["mask"] = np.ascontiguousarray(read_matrix().T)
+                    if L.extra["mask"].shape != L.W.shape:
+                        raise ValueError("Wrong dimensionality of the sparsity mask in network file")
+                    if i < len(toks) and toks[i] == "m":
+                        L.extra["accu"] = np.ascontiguousarray(read_matrix().T)
+                # (no mask matrix: no "mask" key, every weight is active)
             elif tag == "<blockarray>":
                 # cuBlockArray.cc:57-122
                 nb = int(toks[i])
@@ -335,6 +371,31 @@ def gen_discrete_init(dims_in: Sequence[int], dims_out: Sequence[int], seed: int
     n_out, n_in = int(sum(dims_out)), int(sum(dims_in))
     b = (rng.random(n_out) / 5.0 - 4.1).astype(np.float32) if negbias else np.zeros(n_out, np.float32)
     return [Layer("<discretelinearity>", n_out, n_in, None, b, {"Ws": Ws}),
+            Layer("<sigmoid>", n_out, n_out)]
+
+
+def gen_sparse_init(n_in: int, n_out: int, seed: int, density: float = 1.0, gauss: bool = True,
+                    negbias: bool = True) -> List[Layer]:
+    """One <sparselinearity> n_in -> n_out followed by its <sigmoid>, parameters drawn as gen_mlp_init draws a hidden
+    layer's: W^T ~ 0.1 N(0,1) (--gauss) or U[-0.1, 0.1], bias U[-4.1, -3.9] (--negbias) or 0.  density < 1: a random
+    0/1 mask (each weight active with probability `density`, drawn after W and the bias, so W and b do not depend
+    on the density) in extra["mask"], W zeroed under it; density 1: no mask matrix (the file then has none and every
+    weight is active)."""
+    if not 0.0 <= density <= 1.0:
+        raise ValueError("gen_sparse_init: density must lie in [0, 1]")
+    rng = np.random.default_rng(seed)
+    if gauss:
+        Wt = (0.1 * rng.standard_normal((n_out, n_in))).astype(np.float32)
+    else:
+        Wt = (rng.random((n_out, n_in)) / 5.0 - 0.1).astype(np.float32)
+    b = (rng.random(n_out) / 5.0 - 4.1).astype(np.float32) if negbias else np.zeros(n_out, np.float32)
+    W = np.ascontiguousarray(Wt.T)
+    extra = {}
+    if density < 1.0:
+        mask = (rng.random((n_in, n_out)) < density).astype(np.float32)
+        W = W * mask
+        extra["mask"] = mask
+    return [Layer("<sparselinearity>", n_out, n_in, W, b, extra),
             Layer("<sigmoid>", n_out, n_out)]
 
 
