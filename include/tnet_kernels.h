@@ -14,6 +14,8 @@
  *     cukernels.h:11-15); stride is in elements;
  *   - raw device pointers, never owned, never freed here; no allocation inside except in the
  *     documented workspaces the caller passes in;
+ *   - no entry point reads a value from, or writes, anything outside [rows x cols] of an operand unless its own
+ *     comment says so, and padding contents are unspecified (tests/test_gpu_views.py);
  *   - launch geometry is a kernel-internal detail (no dim3 in the ABI, unlike cukernels.h);
  *   - every launch goes on the caller's stream (hipStream_t passed as void*; NULL = default);
  *     no device synchronisation inside (the reference synchronised after every call,
