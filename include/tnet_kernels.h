@@ -15,7 +15,8 @@
  *   - raw device pointers, never owned, never freed here; no allocation inside except in the
  *     documented workspaces the caller passes in;
  *   - no entry point reads a value from, or writes, anything outside [rows x cols] of an operand unless its own
- *     comment says so, and padding contents are unspecified (tests/test_gpu_views.py);
+ *     comment says so, and padding contents are unspecified (tests/test_gpu_views.py for the dense family,
+ *     tests/test_gpu_rnn_views.py for the single-frame chain, tests/test_gpu_rbm_views.py for the RBM step);
  *   - launch geometry is a kernel-internal detail (no dim3 in the ABI, unlike cukernels.h);
  *   - every launch goes on the caller's stream (hipStream_t passed as void*; NULL = default);
  *     no device synchronisation inside (the reference synchronised after every call,
@@ -373,7 +374,8 @@ int tnet_rbm_update_stats(const float* V, TnetMatrixDim dV, const float* H, Tnet
  * update's tiles.  y must lie outside V (TNET_ERR_ARG; the trainer double-buffers the visible statistics).
  * Results identical to the separate calls (y's row padding up to 4 columns may be written too);
  * TNET_ERR_UNSUPPORTED where tnet_rbm_update_stats declines, fewer than 16 CUs are left beside the tiles,
- * or the strides are not 16-B multiples (make the separate calls). */
+ * or y / x are not 16-byte aligned with strides that are multiples of 4 holding roundup4(cols) (make the separate
+ * calls).  V, H, W, corrW as tnet_rbm_update: 16-byte aligned, strides multiples of 4 (else TNET_ERR_ARG). */
 int tnet_rbm_update_stats_gather(const float* V, TnetMatrixDim dV, const float* H, TnetMatrixDim dH, float* W,
                                  TnetMatrixDim dW, float* corrW, int strideCorr, float scale, float mmt, float l2,
                                  int B, float* vb, float* cvb, float* hb, float* chb, double* mse_stats, float* y,
@@ -385,11 +387,19 @@ int tnet_rbm_update_stats_gather(const float* V, TnetMatrixDim dV, const float* 
  *   c_v = mmt*c_v + scale*(sum pos_vis - sum neg_vis) ; vb += c_v
  *   c_h = mmt*c_h + scale*(sum of all rows of Hs)      ; hb += c_h
  *   mse_stats (nullable, stats layout as tnet_mse) += sum (neg_vis - pos_vis)^2.
- * Column sums bit-identical to tnet_rbm_bias_update; no workspace.  TNET_ERR_UNSUPPORTED for B > 4096. */
+ * Column sums bit-identical to tnet_rbm_bias_update; no workspace.  TNET_ERR_UNSUPPORTED for B > 4096.
+ * Any strides, 4-byte aligned pointers (scalar loads); mse_stats 8-byte aligned (TNET_STATS_WORDS doubles). */
 int tnet_rbm_stats_update(const float* Vs, TnetMatrixDim dV, const float* Hs, TnetMatrixDim dH, int B, float* vb,
                           float* cvb, float* hb, float* chb, float scale, float mmt, double* mse_stats, void* stream);
 
-/* ---- single-frame kernels (TRecurrentCu: CuMath::OffsetGemv / BlasGer, cumath.cc:292-362) ---- */
+/* ---- single-frame kernels (TRecurrentCu: CuMath::OffsetGemv / BlasGer, cumath.cc:292-362) ----
+ * Alignment and strides, for every single-frame entry point from here to tnet_rnn_update: float and int operands
+ * need 4-byte alignment only and any leading dimension >= the row length is accepted -- the kernels take their
+ * 16-byte paths only where the row length and the leading dimensions are multiples of 4 and the pointers 16-byte
+ * aligned, and a scalar form otherwise -- with one exception, tnet_rnn_out_full_ahead (W and D 16-byte aligned, ldw
+ * and ldd multiples of 4, else TNET_ERR_UNSUPPORTED: below).  The 8-byte operands (smx, stats, argkey / keys) must be
+ * 8-byte aligned: they are read as doubles or are targets of 64-bit atomics.  Flat operands (partial, opart, dpart,
+ * smx, vout, the workspaces) are addressed densely and hold exactly the element counts stated. */
 /* single-frame forward of the recurrent layer: y = act(b + [v0, v1] W) for the row [v0 (K0), v1 (K1)]
  * read in place, also stored to vout (K0+K1 floats, NULL: not stored) -- CuRecurrent::Propagate's
  * history push + OffsetGemv (cuRecurrent.cc:26-47) in two launches; v1 may alias y. */
@@ -426,7 +436,8 @@ int tnet_gemv_rowvec_softmax_xent(const float* v, int K, const float* W, int ldw
  *                              train: the output layer's backprop + SGD of tnet_affine_bwd_update_row
  *                              (e_out = Wo e, d = e_out .* h (1 - h)); cross-entropy into stats slot 0;
  *                              the frame's argmax folded into *argkey (zero it first) by atomicMax of
- *                              {y bits << 32 | ~column}; y / e / e_out / d may be NULL
+ *                              {y bits << 32 | ~column}: the first column of equal maxima wins; y / e / e_out / d
+ *                              may be NULL; without train, Wo / bo / corrWo / corr_bo / e_out / d are not touched
  *   tnet_argmax_correct      : frame accuracy of T frames from their argmax keys into stats slot 0 */
 int tnet_gemv_rowvec_partial(const float* v0, int K0, const float* v1, int K1, float* vout, const float* W, int ldw,
                              int N, float* partial, void* stream);
@@ -488,7 +499,8 @@ int tnet_affine_bwd_update_row(const float* x, int n_in, const float* e, int n_o
                                const float* s, float* d_out, void* stream);
 /* one frame's tnet_affine_update + tnet_bias_update in one launch (the output layer of TRecurrentCu,
  * cuBiasedLinearity.cc:46-64 with one row): c = x_i e_j (+ mmt corrW); W += scale c; W += l2 W;
- * b += scale (e_j + mmt corr_b). corrW / corr_b may be NULL when mmt == 0. */
+ * b += scale (e_j + mmt corr_b).  With mmt == 0, corrW / corr_b are neither read nor written (and may be NULL);
+ * the same holds for tnet_affine_bwd_update_row and for corrWo / corr_bo of tnet_rnn_out_bwd_update[_ahead]. */
 int tnet_affine_update_row(const float* x, int n_in, const float* e, int n_out, float* W, int ldw, float* corrW,
                            int ldc, float* b, float* corr_b, float scale, float mmt, float l2, void* stream);
 /* workspace bytes for tnet_gemv_rowvec */
@@ -498,7 +510,8 @@ long tnet_gemv_workspace(int K, int N);
 int tnet_gemv_rowvec(const float* v, int K, const float* W, int ldw, const float* b, float* y, int N, int act,
                      void* workspace, void* stream);
 /* y[r] = beta*y[r] + W[r0 + r, 0:n] . x  for r < nrows, then y[r] *= s[r](1 - s[r]) if s != NULL
- * (OffsetGemv('N') with the row offset, and the fused diff-sigmoid of the BPTT step). */
+ * (OffsetGemv('N') with the row offset, and the fused diff-sigmoid of the BPTT step).  Rows of W outside
+ * [r0, r0 + nrows) are not touched; beta == 0 does not read y; n == 0 gives y[r] = beta*y[r] and reads no W, x. */
 int tnet_gemv_rows(const float* W, int ldw, int r0, int nrows, int n, const float* x, float* y, float beta,
                    const float* s, void* stream);
 /* CuRecurrent::Update weight/bias step (cuRecurrent.cc:88-153) in one pass over W [rows x nout]:
@@ -673,7 +686,8 @@ int tnet_sparse_mask_update(float* W, TnetMatrixDim dW, unsigned* bits, int ldma
 /* ---- per-element HybridTaus random numbers (CuRand, curand.tcc / curandkernels.cu) ----------
  * z1..z4: four uint32 state arrays with the element layout of the target matrix (index =
  * col + row*stride), seeded by the caller with lrand48() values > 128 (curand.tcc:36-45) and
- * advanced in place. */
+ * advanced in place.  Any stride >= cols, 4-byte aligned pointers; state words outside [rows x cols] (the
+ * column padding of the state arrays included) are neither read nor written. */
 /* mat = U(0,1) (cudaF_rand, curandkernels.cu:46-52) */
 int tnetF_rand(float* mat, TnetMatrixDim d, unsigned* z1, unsigned* z2, unsigned* z3, unsigned* z4, void* stream);
 /* mat = N(0,1) by Box-Muller (cudaF_gauss_rand, curandkernels.cu:69-77) */

@@ -344,7 +344,8 @@ __global__ __launch_bounds__(256) void gemv_rows_kernel(const float* __restrict_
   const float sv = s ? s[r] : 0.f;
   const float yv = beta != 0.f ? y[r] : 0.f;
   float acc = 0.f;
-  if ((n & 3) == 0 && (ldw & 3) == 0 && (((uintptr_t)row | (uintptr_t)x) & 15) == 0) {
+  // (n == 0 takes the scalar loop, which reads nothing: the register form's clamp n - 4 would lie before the row)
+  if (n > 0 && (n & 3) == 0 && (ldw & 3) == 0 && (((uintptr_t)row | (uintptr_t)x) & 15) == 0) {
     if (n <= 1024) {
       f32x4 a[4], b[4];
 #pragma unroll
@@ -1123,7 +1124,8 @@ extern "C" int tnet_affine_update_row(const float* x, int n_in, const float* e, 
       (mmt != 0.f && (!corrW || !corr_b)))
     return TNET_ERR_ARG;
   affine_update_row_kernel<<<dim3(cdiv(n_out, 256), n_in + 1), 256, 0, (hipStream_t)stream>>>(
-      x, n_in, e, n_out, W, ldw, corrW, ldc, b, mmt != 0.f ? corr_b : nullptr, scale, mmt, l2);
+      x, n_in, e, n_out, W, ldw, mmt != 0.f ? corrW : nullptr, ldc, b, mmt != 0.f ? corr_b : nullptr, scale, mmt,
+      l2);  // (mmt == 0: the momentum buffers are neither read nor written, as in tnet_affine_bwd_update_row)
   TNET_LAUNCH_CHECK();
   return TNET_OK;
 }

@@ -1,4 +1,5 @@
-"""Poisoned caller-owned views for the kernel tests (tests/test_gpu_views.py, tests/test_kernel_views_host.py).
+"""Poisoned caller-owned views for the kernel tests (tests/test_gpu_views.py, tests/test_gpu_rnn_views.py,
+tests/test_gpu_rbm_views.py, tests/test_kernel_views_host.py).
 
 DeviceArray hands every kernel a matrix at an allocation base, with a stride that is a multiple of 64 floats and
 zero-filled padding.  A PoisonView is what the C ABI actually allows: a [rows x cols] window somewhere inside a
@@ -23,6 +24,12 @@ GUARD = 3 rows of S elements above and below):
                                             points whose header allows any stride (the GEMM family rejects it)
 The backing buffer has (GUARD + rows + GUARD) * (c0 + S) words; element (r, c) of the view is word
 (GUARD + r) * S + c0 + c, so .ptr = base + (GUARD * S + c0) * 4.
+
+8-byte operands (float64 / uint64: softmax pairs, statistics accumulators, argmax keys).  The backing buffer stays
+uint32 words and the frame holds the same POISON word, so every check still compares words; an element is two words,
+the geometry is that of a 4-byte view of 2 * cols word columns (.wcols, .wstride; .stride stays in elements), and the
+places a check names are in word columns.  Only `tight` and `offset` exist: c0 and S are even there, so the base is
+8-byte aligned, as the 64-bit atomics and loads on these operands need; asking for `odd` raises ValueError.
 
 What the poison can and cannot show.  A read outside the matrix is visible only when it reaches a stored output:
 NaN times zero is NaN, so a kernel that multiplies a stray operand by a zero weight does not hide it, and a stray
@@ -67,7 +74,7 @@ def host_image(a, rows, cols, layout, dtype=np.float32, poison=POISON):
     c0, S = layout_geometry(cols, layout)
     img = np.full((2 * GUARD + rows) * (c0 + S), poison, np.uint32)
     if a is not None:
-        a = np.ascontiguousarray(np.asarray(a, dtype=dtype).reshape(rows, cols))
+        a = np.ascontiguousarray(np.asarray(a, dtype=dtype)).reshape(rows, -1)  # (cols counts words)
         img[interior_index(rows, cols, layout)] = a.view(np.uint32).reshape(-1)
     return img
 
@@ -124,11 +131,17 @@ class PoisonView:
             dtype = dtype or (np.int32 if a.dtype.kind in "iu" else np.float32)
         self.rows, self.cols, self.layout = int(rows), int(cols), layout
         self.dtype = np.dtype(dtype or np.float32)
-        assert self.dtype.itemsize == 4
-        self.c0, self.stride = layout_geometry(self.cols, layout)
-        self._index = interior_index(self.rows, self.cols, layout)
+        assert self.dtype.itemsize in (4, 8)
+        self.wpe = self.dtype.itemsize // 4  # words per element
+        if self.wpe == 2 and layout not in ("tight", "offset"):
+            raise ValueError(f"an 8-byte view exists only in the tight and offset layouts, not in {layout!r}")
+        self.wcols = self.cols * self.wpe    # the view's width in words: what the geometry and the checks use
+        self.c0, self.wstride = layout_geometry(self.wcols, layout)
+        assert self.wstride % self.wpe == 0 and (GUARD * self.wstride + self.c0) % self.wpe == 0
+        self.stride = self.wstride // self.wpe  # in elements, as the kernels take it
+        self._index = interior_index(self.rows, self.wcols, layout)
         self.poison = np.uint32(poison)
-        img = host_image(a, self.rows, self.cols, layout, self.dtype, self.poison)
+        img = host_image(a, self.rows, self.wcols, layout, self.dtype, self.poison)
         self.words = img.size
         self.initial = img.copy()  # what the buffer held before any call: the `before` of a pure input
         if device:
@@ -136,7 +149,7 @@ class PoisonView:
             self._host = None
             self.backing = DeviceArray(1, self.words, np.uint32, stride=self.words, zero=False)
             self.backing.upload(img.reshape(1, -1))
-            self.ptr = self.backing.ptr + (GUARD * self.stride + self.c0) * 4
+            self.ptr = self.backing.ptr + (GUARD * self.wstride + self.c0) * 4
         else:
             self._host, self.backing, self.ptr = img, None, None
 
@@ -145,8 +158,8 @@ class PoisonView:
         return cls(None, layout, rows, cols, dtype, device)
 
     @classmethod
-    def vector(cls, v, layout, device=True, poison=POISON):
-        return cls(np.asarray(v).reshape(1, -1), layout, device=device, poison=poison)
+    def vector(cls, v, layout, device=True, poison=POISON, dtype=None):
+        return cls(np.asarray(v).reshape(1, -1), layout, dtype=dtype, device=device, poison=poison)
 
     @classmethod
     def empty_vector(cls, n, layout, dtype=np.float32, device=True):
@@ -170,7 +183,7 @@ class PoisonView:
 
 def assert_frame_untouched(view, what="", raw=None):
     """`raw`: a view.raw() the caller already fetched (saves a second copy)"""
-    msg = frame_violation(view.raw() if raw is None else raw, view.rows, view.cols, view.layout, view.poison)
+    msg = frame_violation(view.raw() if raw is None else raw, view.rows, view.wcols, view.layout, view.poison)
     assert msg is None, f"{what}: {msg}"
 
 
@@ -178,6 +191,6 @@ def assert_unchanged(view, before_raw, what=""):
     now = view.raw()
     bad = np.flatnonzero(now != np.asarray(before_raw).view(np.uint32).reshape(-1))
     if bad.size:
-        place, r, c = locate(bad[0], view.rows, view.cols, view.layout)
+        place, r, c = locate(bad[0], view.rows, view.wcols, view.layout)
         raise AssertionError(f"{what}: a pure input changed: {bad.size} word(s), first in the {place} at "
                              f"(row {r}, col {c}) of a {view.rows} x {view.cols} '{view.layout}' view")

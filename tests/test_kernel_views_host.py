@@ -1,6 +1,7 @@
 """The poisoned-view helper (tests/kernel_views.py) checked without a device: the host image is numpy alone, a
 corruption planted anywhere in the frame is caught and located, the interior round-trips exactly.  This is the proof
-that the frame checks of tests/test_gpu_views.py can fail."""
+that the frame checks of tests/test_gpu_views.py, tests/test_gpu_rnn_views.py and tests/test_gpu_rbm_views.py can
+fail.  The 8-byte views (float64 / uint64 interiors over the same uint32 words) have their own cases at the end."""
 import numpy as np
 import pytest
 
@@ -136,3 +137,98 @@ def test_another_nan_in_the_frame_is_a_failure(layout):
         w._host[idx] = np.uint32(1)
         assert frame_violation(w.raw(), 4, 6, layout) is not None
         assert locate(idx, 4, 6, layout)[0] in ("guard rows above", "guard rows below")
+
+
+# ---- 8-byte views (float64 / uint64): two words per element, the same checks on words ------------------------------
+WIDE_LAYOUTS = ("tight", "offset")
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.uint64])
+@pytest.mark.parametrize("layout", WIDE_LAYOUTS)
+@pytest.mark.parametrize("rows,cols", [(1, 1), (1, 3), (1, 130), (3, 5)])
+def test_wide_view_geometry_and_round_trip(rows, cols, layout, dtype):
+    a = (np.arange(rows * cols, dtype=np.uint64) * np.uint64(0x0123456789ABCDEF)).view(dtype).reshape(rows, cols)
+    v = PoisonView(a, layout, dtype=dtype, device=False)
+    c0, S = layout_geometry(2 * cols, layout)
+    assert (v.wpe, v.wcols, v.c0, v.wstride, v.stride) == (2, 2 * cols, c0, S, S // 2)
+    assert c0 % 2 == 0 and S % 2 == 0 and (GUARD * S + c0) % 2 == 0  # the base is 8-byte aligned
+    assert v.words == (2 * GUARD + rows) * (c0 + S)
+    got = v.numpy()
+    assert got.dtype == np.dtype(dtype) and got.shape == (rows, cols)
+    np.testing.assert_array_equal(got.view(np.uint64), a.view(np.uint64))
+    raw = v.raw()
+    assert raw.dtype == np.uint32 and (raw == POISON).sum() == v.words - 2 * rows * cols
+    assert_frame_untouched(v)
+    assert_unchanged(v, raw)
+    e = PoisonView.empty(rows, cols, layout, dtype, device=False)
+    assert (e.raw() == POISON).all()
+    ev = PoisonView.empty_vector(cols, layout, dtype, device=False)
+    assert ev.rows == 1 and ev.wcols == 2 * cols and (ev.raw() == POISON).all()
+    vv = PoisonView.vector(a[0], layout, device=False, dtype=dtype)
+    np.testing.assert_array_equal(vv.numpy()[0].view(np.uint64), a[0].view(np.uint64))
+
+
+def wword(view, r, wc):
+    """backing word of word column wc of row r of an 8-byte view (anywhere in the frame)"""
+    return (GUARD + r) * view.wstride + view.c0 + wc
+
+
+WIDE_PLANTS = [
+    ("column padding", lambda v: (v.rows // 2, v.wcols)),      # the first padding word after a row's last element
+    ("column padding", lambda v: (v.rows - 1, v.wcols + 1)),   # the high word of the element one past the end
+    ("guard rows above", lambda v: (-1, 0)),
+    ("guard rows above", lambda v: (-GUARD, v.wcols - 1)),
+    ("guard rows below", lambda v: (v.rows, 0)),
+    ("guard rows below", lambda v: (v.rows + GUARD - 1, 1)),
+    ("c0 band", lambda v: (0, -1)),                            # the high word of the element before (0, 0)
+    ("c0 band", lambda v: (v.rows - 1, -v.c0)),
+]
+WIDE_PLANT_CASES = [(layout, k) for layout in WIDE_LAYOUTS for k, (place, _) in enumerate(WIDE_PLANTS)
+                    if not (place == "c0 band" and layout == "tight")]
+
+
+@pytest.mark.parametrize("rows,cols", [(1, 3), (3, 5)])   # 6 and 10 word columns: padding in both layouts
+@pytest.mark.parametrize("layout,k", WIDE_PLANT_CASES)
+def test_wide_view_planted_word_is_caught_and_located(rows, cols, layout, k):
+    place, where = WIDE_PLANTS[k]
+    v = PoisonView(np.ones((rows, cols)), layout, dtype=np.float64, device=False)
+    assert v.wstride - v.c0 > v.wcols + 1
+    r, wc = where(v)
+    before = v.raw()
+    v._host[wword(v, r, wc)] = np.uint32(0)
+    with pytest.raises(AssertionError) as ei:
+        assert_frame_untouched(v, "planted")
+    msg = str(ei.value)
+    assert place in msg and f"(row {r}, col {wc})" in msg, msg
+    with pytest.raises(AssertionError):
+        assert_unchanged(v, before, "planted")
+    # one word of an interior element is not the frame
+    v2 = PoisonView(np.ones((rows, cols)), layout, dtype=np.float64, device=False)
+    v2._host[wword(v2, rows - 1, v2.wcols - 1)] = np.uint32(7)
+    assert_frame_untouched(v2)
+
+
+@pytest.mark.parametrize("layout", WIDE_LAYOUTS)
+@pytest.mark.parametrize("half", [0, 1])
+def test_wide_pure_input_changed_interior_is_caught(layout, half):
+    """either word of an element of a pure 8-byte input (softmax pairs, argmax keys)"""
+    keys = np.arange(1, 8, dtype=np.uint64) << np.uint64(33)
+    v = PoisonView.vector(keys, layout, device=False, poison=POISON_INPUT, dtype=np.uint64)
+    assert not (v.raw() == POISON).any()
+    assert_unchanged(v, v.initial)
+    v._host[wword(v, 0, 2 * 3 + half)] ^= np.uint32(1)
+    assert_frame_untouched(v)  # the frame is intact: only assert_unchanged sees it
+    with pytest.raises(AssertionError, match="interior.*row 0, col %d" % (6 + half)):
+        assert_unchanged(v, v.initial, "keys")
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.uint64])
+def test_wide_view_refuses_the_odd_layout(dtype):
+    """a misaligned address must never reach a 64-bit atomic: the request fails in Python"""
+    for make in (lambda: PoisonView(np.zeros((1, 4)), "odd", dtype=dtype, device=False),
+                 lambda: PoisonView.empty(2, 3, "odd", dtype, device=False),
+                 lambda: PoisonView.empty_vector(5, "odd", dtype, device=False),
+                 lambda: PoisonView.vector(np.zeros(5), "odd", device=False, dtype=dtype)):
+        with pytest.raises(ValueError, match="8-byte"):
+            make()
+    PoisonView(np.zeros((1, 4), np.float32), "odd", device=False)  # 4-byte views keep it
