@@ -1,5 +1,5 @@
 """Poisoned caller-owned views for the kernel tests (tests/test_gpu_views.py, tests/test_gpu_rnn_views.py,
-tests/test_gpu_rbm_views.py, tests/test_kernel_views_host.py).
+tests/test_gpu_rbm_views.py, tests/test_gpu_layer_views.py, tests/test_kernel_views_host.py).
 
 DeviceArray hands every kernel a matrix at an allocation base, with a stride that is a multiple of 64 floats and
 zero-filled padding.  A PoisonView is what the C ABI actually allows: a [rows x cols] window somewhere inside a
@@ -10,7 +10,8 @@ fixed quiet-NaN bit pattern (POISON).
   PoisonView(a, layout)              a in the interior, poison everywhere else
   PoisonView.empty(r, c, layout)     the interior is poison too: an output must write every element
   PoisonView.vector(v, layout)       a 1 x n view (bias, momentum, scale[], slab-sum rows, class ids, row indices):
-                                     a poisoned band before and after, 16-B aligned in `tight` / `offset`
+                                     a poisoned band before and after, 16-B aligned in `tight` / `offset`,
+                                     4-B aligned (4 bytes past a 16-B boundary) in `shifted` / `odd`
   assert_frame_untouched(view)       every word of the backing buffer outside [rows x cols] is still POISON
                                      (compared as uint32: another NaN is a failure too); names the first offender
   assert_unchanged(view, before)     the whole backing buffer is bit-identical to `before` (view.raw() taken
@@ -20,6 +21,9 @@ Layouts (S = row stride in elements, c0 = elements between the 16-B aligned row 
 GUARD = 3 rows of S elements above and below):
   tight    c0 = 0, S = roundup4(cols)       no padding at all where cols % 4 == 0
   offset   c0 = 4, S = roundup4(cols) + 12  rows neither 64-float nor 256-B aligned; the base 16-B aligned, no more
+  shifted  c0 = 1, S = roundup4(cols) + 8   the base 4 bytes past a 16-B boundary, the stride a multiple of 4: the
+                                            least the shared / discrete / sparse layer kernels' headers allow
+                                            (every row origin is off 16 bytes: their masked scalar loads)
   odd      c0 = 1, S = cols + 3             a 4-B aligned base and a stride that is no multiple of 4: only for entry
                                             points whose header allows any stride (the GEMM family rejects it)
 The backing buffer has (GUARD + rows + GUARD) * (c0 + S) words; element (r, c) of the view is word
@@ -29,7 +33,8 @@ The backing buffer has (GUARD + rows + GUARD) * (c0 + S) words; element (r, c) o
 uint32 words and the frame holds the same POISON word, so every check still compares words; an element is two words,
 the geometry is that of a 4-byte view of 2 * cols word columns (.wcols, .wstride; .stride stays in elements), and the
 places a check names are in word columns.  Only `tight` and `offset` exist: c0 and S are even there, so the base is
-8-byte aligned, as the 64-bit atomics and loads on these operands need; asking for `odd` raises ValueError.
+8-byte aligned, as the 64-bit atomics and loads on these operands need; asking for `shifted` or `odd` (c0 odd)
+raises ValueError.
 
 What the poison can and cannot show.  A read outside the matrix is visible only when it reaches a stored output:
 NaN times zero is NaN, so a kernel that multiplies a stray operand by a zero weight does not hide it, and a stray
@@ -51,7 +56,7 @@ import numpy as np
 POISON = np.uint32(0x7FC5A5A5)        # a quiet NaN with a recognisable payload
 POISON_INPUT = np.uint32(0x7FC1D00D)  # the same for a pure input's buffer (see the module docstring)
 GUARD = 3
-LAYOUTS = ("tight", "offset", "odd")
+LAYOUTS = ("tight", "offset", "shifted", "odd")
 
 
 def roundup4(n):
@@ -64,6 +69,8 @@ def layout_geometry(cols, layout):
         return 0, roundup4(cols)
     if layout == "offset":
         return 4, roundup4(cols) + 12
+    if layout == "shifted":
+        return 1, roundup4(cols) + 8
     if layout == "odd":
         return 1, int(cols) + 3
     raise ValueError(f"unknown layout {layout!r}")
@@ -134,7 +141,7 @@ class PoisonView:
         assert self.dtype.itemsize in (4, 8)
         self.wpe = self.dtype.itemsize // 4  # words per element
         if self.wpe == 2 and layout not in ("tight", "offset"):
-            raise ValueError(f"an 8-byte view exists only in the tight and offset layouts, not in {layout!r}")
+            raise ValueError(f"an 8-byte view exists only in the tight and offset layouts (c0 even), not in {layout!r}")
         self.wcols = self.cols * self.wpe    # the view's width in words: what the geometry and the checks use
         self.c0, self.wstride = layout_geometry(self.wcols, layout)
         assert self.wstride % self.wpe == 0 and (GUARD * self.wstride + self.c0) % self.wpe == 0

@@ -41,7 +41,9 @@ from tnet_amd._lib import MatrixDim, check, lib  # noqa: E402
 
 ERR_ARG = -1
 EPS = 2.0 ** -24
-LAYOUTS = ("tight", "offset")   # the entry points take strides that are multiples of 4 only
+# the entry points take strides that are multiples of 4 only; `shifted` is the least they allow, a base 4 bytes past
+# a 16-byte boundary: X and E then go through the masked scalar loads
+LAYOUTS = ("tight", "offset", "shifted")
 
 
 def S():

@@ -21,7 +21,9 @@ from tnet_amd import DeviceArray, Network, Objective, Trainer, TnetError, format
 from tnet_amd._lib import check, lib  # noqa: E402
 
 # (rows, N, in, out): a single element; the fixture's layer; unaligned windows (N*in = 429 is not the pitch);
-# several tiles per instance with ragged edges; odd everything; the 128x128 tile's shape class
+# several tiles per instance with ragged edges; odd everything; a deep K with whole 64x64 tiles (pick_tile counts
+# cdiv(M,128) * cdiv(N,128) * batch = 10 forward, 40 backward, 20 for the update: below the 200 from which the
+# 128x128 tile runs -- tests/test_gpu_layer_views.py reaches that one, through the batch)
 SHAPES = [(1, 1, 1, 1), (16, 3, 24, 16), (33, 11, 39, 10), (130, 5, 72, 136), (45, 2, 37, 50), (256, 5, 440, 128)]
 
 

@@ -53,8 +53,10 @@ def test_geometry(rows, cols, layout):
         assert c0 == 0 and S == roundup4(cols) and origin % 4 == 0
     elif layout == "offset":
         assert c0 == 4 and S == roundup4(cols) + 12 and origin % 4 == 0
+    elif layout == "shifted":
+        assert c0 == 1 and S == roundup4(cols) + 8 and S % 4 == 0 and origin % 4 == 1
     else:
-        assert c0 == 1 and S == cols + 3
+        assert layout == "odd" and c0 == 1 and S == cols + 3
     # the last interior element lies inside the buffer with GUARD whole rows after it
     assert word(v, rows - 1, cols - 1) + GUARD * S < v.words
 
@@ -80,6 +82,28 @@ def test_interior_round_trips_and_frame_is_poison(rows, cols, layout):
     # an empty view: the interior is poison as well
     e = PoisonView.empty(rows, cols, layout, device=False)
     assert (e.raw() == POISON).all() and np.isnan(e.numpy()).all()
+
+
+@pytest.mark.parametrize("cols", [1, 3, 4, 5, 10, 39, 64, 136, 429, 8532])
+@pytest.mark.parametrize("rows", [0, 1, 33])
+def test_shifted_is_the_least_the_layer_kernels_allow(rows, cols):
+    """the base 4 bytes past a 16-byte boundary (the backing buffer is an allocation: 16-byte aligned and more), the
+    stride a multiple of 4 elements -- so every row origin is off 16 bytes by the same 4 -- and the view's pointer
+    is where element (0, 0) lies"""
+    c0, S = layout_geometry(cols, "shifted")
+    assert (GUARD * S + c0) * 4 % 16 == 4 and S % 4 == 0 and S >= cols + 8
+    v = PoisonView(np.arange(rows * cols, dtype=np.float32).reshape(rows, cols), "shifted", rows=rows, cols=cols,
+                   device=False) if rows else PoisonView.empty(0, cols, "shifted", device=False)
+    assert (v.c0, v.stride) == (c0, S)
+    for r in range(rows):
+        assert word(v, r, 0) * 4 % 16 == 4
+    if rows:
+        assert v.raw()[word(v, 0, 0)] == np.float32(0).view(np.uint32)
+        assert v.raw()[word(v, rows - 1, cols - 1)] == np.float32(rows * cols - 1).view(np.uint32)
+        assert v.raw()[word(v, 0, -1)] == POISON and v.raw()[word(v, rows - 1, cols)] == POISON
+    # a vector (bias, packed parameters, mask words as one row) is 4-byte aligned in the same way
+    vec = PoisonView.vector(np.zeros(cols, np.float32), "shifted", device=False)
+    assert word(vec, 0, 0) * 4 % 16 == 4 and vec.rows == 1
 
 
 def plant(view, r, c, value=np.uint32(0)):
@@ -232,3 +256,11 @@ def test_wide_view_refuses_the_odd_layout(dtype):
         with pytest.raises(ValueError, match="8-byte"):
             make()
     PoisonView(np.zeros((1, 4), np.float32), "odd", device=False)  # 4-byte views keep it
+    # `shifted` has an odd c0 too: its base is 4 bytes past a 16-byte boundary, never 8-byte aligned
+    for make in (lambda: PoisonView(np.zeros((1, 4)), "shifted", dtype=dtype, device=False),
+                 lambda: PoisonView.empty(2, 3, "shifted", dtype, device=False),
+                 lambda: PoisonView.empty_vector(5, "shifted", dtype, device=False),
+                 lambda: PoisonView.vector(np.zeros(5), "shifted", device=False, dtype=dtype)):
+        with pytest.raises(ValueError, match="8-byte"):
+            make()
+    PoisonView(np.zeros((1, 4), np.float32), "shifted", device=False)
