@@ -728,6 +728,33 @@ int tnet_mse(const float* Y, TnetMatrixDim dY, const float* D, int strideD, floa
 /* Synchronous read-back of a stats accumulator: totals of the error and correct slots. */
 int tnet_stats_fetch(const double* stats, double* error, double* correct, void* stream);
 
+/* ----------------------------------------------------------------------------------
+ * <blocksoftmax>: several softmaxes side by side in one output layer (BlockSoftmax, TNetLib
+ * Activation.cc:55-133; the reference has no GPU form).  Block j covers the columns
+ * [offsets[j], offsets[j+1]); offsets is a DEVICE array of B + 1 ints, offsets[0] = 0,
+ * offsets[B] = cols, ascending (the kernels clamp every entry to [0, cols]).  One launch per call,
+ * rows of up to 4096 columns are read once and held in registers, no floating-point atomics on an
+ * output matrix.
+ * ---------------------------------------------------------------------------------- */
+/* y = softmax of every block on the block's own maximum and sum (Activation.cc:80-103) */
+int tnetF_block_softmax(float* y, const float* x, TnetMatrixDim d, const int* offsets, int B, void* stream);
+/* The fused objective for class-id labels (forward + CrossEntropy::Evaluate + BlockSoftmax's backward):
+ *   Y = block softmax(Z row)    -> written if Y != NULL
+ *   E = y - onehot(label) in the label's block, +0.0f in every other block (the block found from the label
+ *       in offsets; label < 0 or >= cols: an unlabeled row, its whole error +0.0f)
+ *   xent += -log(max(y[label], FLT_MIN)); correct += #(argmax over the WHOLE row of y == label, column 0 for
+ *   an unlabeled row) -- the reference's accounting; stats as tnet_softmax_xent.
+ * With B == 1 Y, the stats and E of labelled rows are tnet_softmax_xent's bit for bit.  The same Y (and, in the
+ * label's block, E) as tnetF_block_softmax -> tnet_softmax_xent(Z = NULL) -> tnet_block_softmax_bwd. */
+int tnet_block_softmax_xent(const float* Z, TnetMatrixDim dZ, const int* offsets, int B, const int* labels, float* Y,
+                            int strideY, float* E, int strideE, double* stats, void* stream);
+/* BlockSoftmax::BackpropagateFnc (Activation.cc:110-133) for an error no fused call made: per row and block
+ * the sum s of Ein: -0.1 < s < 0.1 copies the block (it held the target), 0.9 < s < 1.1 zeroes it (inactive);
+ * any other sum (the reference's "Invalid sum" error) zeroes it too and adds 1 to *invalid (device int, may be
+ * NULL).  Eout may be Ein. */
+int tnet_block_softmax_bwd(const float* Ein, TnetMatrixDim dE, const int* offsets, int B, float* Eout, int strideEout,
+                           int* invalid, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -242,6 +242,16 @@ int tnet_net_sparse_set(TnetNetwork* net, int i, const float* W, const float* b,
 int tnet_net_sparse_thresholds(TnetNetwork* net, int i, float sparsify_threshold, float unsparsify_accu);
 int tnet_net_sparse_update_mask(TnetNetwork* net, int i);
 
+/* ---- <blocksoftmax> (BlockSoftmax, TNetLib Activation.cc:55-133) ----------------------------------
+ * dims: the block widths of component i; returns the block count B (or a negative status) and copies the first
+ * min(B, cap) widths into dims (dims may be NULL with cap 0 -- ask for the count first).
+ * invalid: the number of (row, block) error sums the component's Backpropagate has met so far that were neither
+ * about 0 nor about 1 (the reference's "Invalid sum" error; such a block's error is zeroed) -- one small
+ * device-to-host copy, made here only; reset != 0 clears the counter after reading.  The fused training step
+ * masks by the label and never counts.  Another component type is an error. */
+int tnet_net_blocksoftmax_dims(TnetNetwork* net, int i, int* dims, int cap);
+int tnet_net_blocksoftmax_invalid(TnetNetwork* net, int i, long* count, int reset);
+
 /* ---- data parallel (no reference counterpart: Platform.h:143-391 is the CPU analogue) ---- */
 int tnet_comm_unique_id(char out[128]);        /* rank 0 creates, the launcher broadcasts it */
 TnetComm* tnet_comm_create(int rank, int world, const char id[128]);

@@ -746,6 +746,29 @@ int tnet_net_sparse_update_mask(TnetNetwork* h, int i) {
   TRY_END
 }
 
+// -------------------------------------------------------------------------- <blocksoftmax>
+static CuBlockSoftmax& blocksoftmax_layer(TnetNetwork* h, int i) {
+  if (i < 0 || i >= h->net.Layers()) Error("component index out of range");
+  auto* p = dynamic_cast<CuBlockSoftmax*>(&h->net.Layer(i));
+  if (!p) Error("component is not <blocksoftmax>");
+  return *p;
+}
+int tnet_net_blocksoftmax_dims(TnetNetwork* h, int i, int* dims, int cap) {
+  try {
+    CuBlockSoftmax& L = blocksoftmax_layer(h, i);
+    for (int k = 0; dims && k < cap && k < L.NBlocks(); ++k) dims[k] = L.Dims()[(size_t)k];
+    return L.NBlocks();
+  } catch (std::exception& e) {
+    g_last_error = e.what();
+    return TNET_ERR_RUNTIME;
+  }
+}
+int tnet_net_blocksoftmax_invalid(TnetNetwork* h, int i, long* count, int reset) {
+  TRY_BEGIN const long n = blocksoftmax_layer(h, i).InvalidSums(reset != 0);
+  if (count) *count = n;
+  TRY_END
+}
+
 // ------------------------------------------------------------------------------ recurrent
 static CuRecurrent& rnn_layer(TnetNetwork* h, int i) {
   if (i < 0 || i >= h->net.Layers()) Error("component index out of range");

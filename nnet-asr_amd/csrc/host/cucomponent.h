@@ -34,6 +34,7 @@ class CuComponent {
     ACT_FUN = 0x0200,
     SOFTMAX,
     SIGMOID,
+    BLOCK_SOFTMAX,
 
     OTHER = 0x0400,
     EXPAND,

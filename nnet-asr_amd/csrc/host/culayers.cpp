@@ -1,4 +1,4 @@
-// culayers.cpp -- <biasedlinearity>, <sigmoid>, <softmax> on the fused gfx950 kernels.
+// culayers.cpp -- <biasedlinearity>, <sigmoid>, <softmax>, <blocksoftmax> on the fused gfx950 kernels.
 #include "culayers.h"
 
 #include "gradexchange.h"
@@ -498,6 +498,72 @@ void CuSoftmax::PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& 
 void CuSoftmax::BackpropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
   // we assume X is already dE/dSoftmax_input (cuActivation.cc:37-40)
   Y.CopyFrom(X);
+}
+
+// ----------------------------------------------------------------------- <blocksoftmax>
+void CuBlockSoftmax::ReadFromStream(std::istream& rIn) {
+  // Vector<int> in the reference's text form: v <B>  d_0 ... d_{B-1}  (Activation.cc:55-71)
+  rIn >> std::ws;
+  if (rIn.peek() != 'v') Error("<blocksoftmax>: expected the block dimensions 'v B d_0 ...'");
+  rIn.get();
+  long long n = -1;
+  rIn >> n;
+  if (rIn.fail() || n < 1 || n > (long long)GetNOutputs()) Error("<blocksoftmax>: invalid number of blocks");
+  std::vector<int> dims((size_t)n);
+  for (auto& d : dims) {
+    rIn >> d;
+    if (rIn.fail()) Error("<blocksoftmax>: truncated block dimensions");
+  }
+  SetDims(dims);
+}
+
+void CuBlockSoftmax::SetDims(const std::vector<int>& dims) {
+  std::vector<int> off(dims.size() + 1);
+  long sum = 0;
+  for (size_t j = 0; j < dims.size(); j++) {
+    if (dims[j] <= 0) Error("<blocksoftmax>: non-positive block dimension " + std::to_string(dims[j]));
+    off[j] = (int)sum;
+    sum += dims[j];
+  }
+  if (dims.empty() || sum != (long)GetNOutputs()) {
+    std::ostringstream os;
+    os << "Non-matching dimension of sum of softmaxes, the sum:" << sum << " GetNOutputs:" << GetNOutputs();
+    Error(os.str());
+  }
+  if (GetNInputs() != GetNOutputs()) Error("<blocksoftmax>: the numbers of inputs and outputs differ");
+  off[dims.size()] = (int)sum;
+  mDim = dims;
+  mOffsets.CopyFromHost(off.data(), off.size());
+  mInvalid.Init(1);
+  mInvalid.SetZero();
+}
+
+void CuBlockSoftmax::WriteToStream(std::ostream& rOut) {
+  rOut << "v " << mDim.size() << "  ";  // Vector.tcc:550-571
+  for (int d : mDim) rOut << d << " ";
+  rOut << "\n";
+}
+
+void CuBlockSoftmax::PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  if (mDim.empty()) Error("<blocksoftmax>: no block dimensions set");
+  if (X.Stride() != Y.Stride()) Error("<blocksoftmax>: input and output strides differ");
+  TNET_SAFE_CALL(tnetF_block_softmax(Y.pCUData(), X.pCUData(), X.Dim(), mOffsets.pCUData(), NBlocks(), S));
+}
+
+void CuBlockSoftmax::BackpropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) {
+  // X is dE/d(softmax input) of the whole row as the objective formed it: only the block that held the target
+  // passes (Activation.cc:110-133)
+  if (mDim.empty()) Error("<blocksoftmax>: no block dimensions set");
+  TNET_SAFE_CALL(tnet_block_softmax_bwd(X.pCUData(), X.Dim(), mOffsets.pCUData(), NBlocks(), Y.pCUData(),
+                                        (int)Y.Stride(), mInvalid.pCUData(), S));
+}
+
+long CuBlockSoftmax::InvalidSums(bool reset) {
+  if (mDim.empty()) return 0;
+  int n = 0;
+  mInvalid.CopyToHost(&n);
+  if (reset) mInvalid.SetZero();
+  return n;
 }
 
 }  // namespace TNet

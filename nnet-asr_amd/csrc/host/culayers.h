@@ -139,6 +139,36 @@ class CuSoftmax : public CuComponent {
   void BackpropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) override;
 };
 
+/// <blocksoftmax>: one softmax per block of columns (BlockSoftmax, TNetLib Activation.h:60-96, .cc:55-133; the
+/// reference's CUDA library has no such component).  The block offsets live on the device from ReadFromStream
+/// on; a step copies nothing to the device and allocates nothing.
+class CuBlockSoftmax : public CuComponent {
+ public:
+  CuBlockSoftmax(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
+  ComponentType GetType() const override { return BLOCK_SOFTMAX; }
+  const char* GetName() const override { return "<blocksoftmax>"; }
+
+  void ReadFromStream(std::istream& rIn) override;
+  void WriteToStream(std::ostream& rOut) override;
+  /// the block widths (programmatic construction; ReadFromStream ends here)
+  void SetDims(const std::vector<int>& dims);
+
+  const std::vector<int>& Dims() const { return mDim; }
+  int NBlocks() const { return (int)mDim.size(); }
+  /// device int[NBlocks() + 1]: offsets[0] = 0, offsets[NBlocks()] = GetNOutputs()
+  const int* Offsets() const { return mOffsets.pCUData(); }
+  /// error-block sums Backpropagate found to be neither ~0 nor ~1 (a device-to-host copy; never on a step's path)
+  long InvalidSums(bool reset);
+
+ protected:
+  void PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) override;
+  void BackpropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) override;
+
+  std::vector<int> mDim;
+  CuVector<int> mOffsets;
+  CuVector<int> mInvalid;  ///< one device counter
+};
+
 /// Fast text parsing of "m R C ..." / "v N ..." blocks (strtof on a buffered stream).
 void ReadMatrixFast(std::istream& in, Matrix<BaseFloat>& m);
 void ReadVectorFast(std::istream& in, Vector<BaseFloat>& v);

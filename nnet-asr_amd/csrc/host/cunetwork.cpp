@@ -53,9 +53,13 @@ void CuNetwork::Propagate(const CuMatrix<BaseFloat>& in, CuMatrix<BaseFloat>& ou
   out.CopyFrom(mNetComponents.back()->GetOutput());
 }
 
-void CuNetwork::Backpropagate(const CuMatrix<BaseFloat>& globerr) {
-  mNetComponents.back()->SetErrorInput(globerr);
-  for (auto it = mNetComponents.rbegin(); it != mNetComponents.rend(); ++it) {
+void CuNetwork::Backpropagate(const CuMatrix<BaseFloat>& globerr, size_t skip_top) {
+  // skip_top: that many components at the top have been dealt with (BlockSoftmaxObjective); globerr is the error
+  // input of the first one below them
+  if (skip_top >= mNetComponents.size()) return;
+  auto first = mNetComponents.rbegin() + (long)skip_top;
+  (*first)->SetErrorInput(globerr);
+  for (auto it = first; it != mNetComponents.rend(); ++it) {
     if (*it != mpPropagErrorStopper) (*it)->Backpropagate();
     if ((*it)->IsUpdatable()) {
       CuUpdatableComponent& rComp = dynamic_cast<CuUpdatableComponent&>(**it);
@@ -161,6 +165,8 @@ CuComponent* CuNetwork::ComponentFactory(std::istream& rIn) {
   if (tag == "<biasedlinearity>") pRet = new CuBiasedLinearity(nInputs, nOutputs, pPred);
   else if (tag == "<sigmoid>") pRet = new CuSigmoid(nInputs, nOutputs, pPred);
   else if (tag == "<softmax>") pRet = new CuSoftmax(nInputs, nOutputs, pPred);
+  // one softmax per block of outputs (multi-task output layers; TNetLib Nnet.cc:249-275, CPU-only in the reference)
+  else if (tag == "<blocksoftmax>") pRet = new CuBlockSoftmax(nInputs, nOutputs, pPred);
   else if (tag == "<rbm>") pRet = new CuRbm(nInputs, nOutputs, pPred);
   else if (tag == "<recurrent>") pRet = new CuRecurrent(nInputs, nOutputs, pPred);
   // convolutive-bottleneck / universal-context layers (cuNetwork.cc:286, 303)
@@ -197,18 +203,51 @@ bool CuNetwork::IsFusableMLP() const {
   for (size_t i = 0; i < n; i += 2) {
     if (mNetComponents[i]->GetType() != CuComponent::BIASED_LINEARITY) return false;
     const bool last = (i + 2 == n);
-    const CuComponent::ComponentType want = last ? CuComponent::SOFTMAX : CuComponent::SIGMOID;
-    if (mNetComponents[i + 1]->GetType() != want) return false;
+    const CuComponent::ComponentType have = mNetComponents[i + 1]->GetType();
+    // (a <blocksoftmax> top: the step is the same below the objective, whose error arrives masked)
+    if (last ? (have != CuComponent::SOFTMAX && have != CuComponent::BLOCK_SOFTMAX) : have != CuComponent::SIGMOID)
+      return false;
   }
   return true;
 }
 
 void CuNetwork::TrainBunchGeneric(const CuMatrix<BaseFloat>& X, const CuVector<int>& labels,
                                   CuObjectiveFunction& obj, bool train) {
+  if (BlockSoftmaxObjective(X, labels, obj)) {
+    if (train) Backpropagate(mGlobErr, 1);
+    RestoreTopWiring();
+    return;
+  }
   CuMatrix<BaseFloat> out;
   Propagate(X, out);
   obj.EvaluateLabels(out, labels, mGlobErr);
   if (train) Backpropagate(mGlobErr);
+}
+
+bool CuNetwork::BlockSoftmaxObjective(const CuMatrix<BaseFloat>& X, const CuVector<int>& labels,
+                                      CuObjectiveFunction& obj) {
+  // a <blocksoftmax> on top under cross-entropy with class-id labels: propagate to the component below it, then
+  // ONE call for its forward pass, the objective and its backward pass -- Y into the component's output, the
+  // error of the label's block into mGlobErr (every other block zero), which is already what the component's
+  // Backpropagate would hand down
+  if (mNetComponents.size() < 2 || mNetComponents.back()->GetType() != CuComponent::BLOCK_SOFTMAX ||
+      obj.GetTypeId() != CuObjectiveFunction::CROSS_ENTROPY)
+    return false;
+  auto* bs = static_cast<CuBlockSoftmax*>(mNetComponents.back());
+  if (X.Cols() != GetNInputs()) Error("CuNetwork::TrainBunch: non-matching input dim");
+  if (labels.Dim() != X.Rows()) Error("CuNetwork::TrainBunch: number of labels != rows");
+  mNetComponents.front()->SetInput(X);
+  for (size_t i = 0; i + 1 < mNetComponents.size(); i++) mNetComponents[i]->Propagate();
+  const CuMatrix<BaseFloat>& Z = bs->GetInput();
+  CuMatrix<BaseFloat>& Y = bs->Output();
+  Y.Init(Z.Rows(), bs->GetNOutputs());
+  mGlobErr.Init(Z.Rows(), bs->GetNOutputs());
+  TNET_SAFE_CALL(tnet_block_softmax_xent(Z.pCUData(), Z.Dim(), bs->Offsets(), bs->NBlocks(), labels.pCUData(),
+                                         Y.pCUData(), (int)Y.Stride(), mGlobErr.pCUData(), (int)mGlobErr.Stride(),
+                                         obj.DeviceStats(), S));
+  obj.AddFrames(Z.Rows());
+  mNetComponents[mNetComponents.size() - 2]->SetErrorInput(mGlobErr);
+  return true;
 }
 
 void CuNetwork::CheckDataParallel(const GradExchange& exchange) const {
@@ -240,14 +279,20 @@ void CuNetwork::CheckDataParallel(const GradExchange& exchange) const {
   }
 }
 
-void CuNetwork::DataParallelBackward(GradExchange& exchange, size_t grows, bool empty) {
+void CuNetwork::RestoreTopWiring() {
+  // after BlockSoftmaxObjective: the component below the top one reads the top one's error output again
+  const size_t n = mNetComponents.size();
+  if (n >= 2) mNetComponents[n - 2]->SetErrorInput(mNetComponents[n - 1]->GetErrorOutput());
+}
+
+void CuNetwork::DataParallelBackward(GradExchange& exchange, size_t grows, bool empty, size_t skip_top) {
   // Per component, top down to the stopper: its backward GEMM first (the last reader of the pre-update W), then
   // its gradient and the reduction; the apply on the exchange's apply stream right behind the reduction, beside
   // the backward passes below, with the parameter gather of the sharded form -- or, once a transport has handed
   // out no apply stream, after every submission, each behind its own reduction (the MLP step's submit_layer)
   std::vector<CuUpdatableComponent*> submitted;
   int n_submitted = 0;
-  for (auto it = mNetComponents.rbegin(); it != mNetComponents.rend(); ++it) {
+  for (auto it = mNetComponents.rbegin() + (long)skip_top; it != mNetComponents.rend(); ++it) {
     CuComponent* c = *it;
     const bool stopper = c == mpPropagErrorStopper;
     if (!empty && !stopper) c->Backpropagate();
@@ -340,6 +385,11 @@ void CuNetwork::TrainBunch(const CuMatrix<BaseFloat>& X, const CuVector<int>& la
     if (IsFusableMLP()) Error("CuNetwork::TrainBunch: data-parallel training of the sigmoid MLP needs cross-entropy");
     // the data-parallel generic step: refused before anything is enqueued where a trained component cannot split
     CheckDataParallel(*exchange);
+    if (BlockSoftmaxObjective(X, labels, obj)) {
+      DataParallelBackward(*exchange, exchange->GlobalRows(X.Rows()), false, 1);
+      RestoreTopWiring();
+      return;
+    }
     CuMatrix<BaseFloat> out;
     Propagate(X, out);
     obj.EvaluateLabels(out, labels, mGlobErr);
@@ -373,6 +423,9 @@ void CuNetwork::TrainBunch(const CuMatrix<BaseFloat>& X, const CuVector<int>& la
 
   // objective outputs: the error (+ the softmax output when kept)
   CuComponent* smx = mNetComponents.back();
+  // a <blocksoftmax> top: its own fused objective (never the <= 256-class fused top layer, a plain softmax); the
+  // error it writes is masked to the label's block, and everything below runs on that matrix unchanged
+  CuBlockSoftmax* block_top = smx->GetType() == CuComponent::BLOCK_SOFTMAX ? static_cast<CuBlockSoftmax*>(smx) : nullptr;
   float* yout = nullptr;
   int ystride = 0;
   if (mKeepOutput) {
@@ -400,7 +453,7 @@ void CuNetwork::TrainBunch(const CuMatrix<BaseFloat>& X, const CuVector<int>& la
     const std::string shape = std::to_string(lin->GetNInputs()) + "x" + std::to_string(lin->GetNOutputs());
     // TNET_FUSED_TOP=0: the three-call form (A/B measurements)
     static const bool fuse_top = !(getenv("TNET_FUSED_TOP") && getenv("TNET_FUSED_TOP")[0] == '0');
-    if (last && fuse_top && lin->GetNOutputs() <= TNET_AFFINE_SOFTMAX_MAX_N) {
+    if (last && fuse_top && !block_top && lin->GetNOutputs() <= TNET_AFFINE_SOFTMAX_MAX_N) {
       // up to 256 classes: logits, softmax, xent, error and the error's slab sums in one pass
       float* cp = nullptr;
       int ldcp = 0;
@@ -436,8 +489,13 @@ void CuNetwork::TrainBunch(const CuMatrix<BaseFloat>& X, const CuVector<int>& la
     CuMatrix<BaseFloat>& logits = mNetComponents[2 * (nl - 1)]->Output();
     KTScope kts("softmax_xent:" + std::to_string(GetNOutputs()),
                 (double)rows * GetNOutputs() * 4.0 * (mKeepOutput ? 3 : 2) + rows * 4.0);
-    TNET_SAFE_CALL(tnet_softmax_xent(logits.pCUData(), logits.Dim(), labels.pCUData(), yout, ystride, mGlobErr.pCUData(),
-                                     (int)mGlobErr.Stride(), obj.DeviceStats(), S));
+    if (block_top)
+      TNET_SAFE_CALL(tnet_block_softmax_xent(logits.pCUData(), logits.Dim(), block_top->Offsets(), block_top->NBlocks(),
+                                             labels.pCUData(), yout, ystride, mGlobErr.pCUData(),
+                                             (int)mGlobErr.Stride(), obj.DeviceStats(), S));
+    else
+      TNET_SAFE_CALL(tnet_softmax_xent(logits.pCUData(), logits.Dim(), labels.pCUData(), yout, ystride,
+                                       mGlobErr.pCUData(), (int)mGlobErr.Stride(), obj.DeviceStats(), S));
   }
   obj.AddFrames(rows);
   if (!train) return;

@@ -42,7 +42,7 @@ class CuNetwork {
   /// forward the data to the output
   void Propagate(const CuMatrix<BaseFloat>& in, CuMatrix<BaseFloat>& out);
   /// backpropagate the error while updating weights
-  void Backpropagate(const CuMatrix<BaseFloat>& globerr);
+  void Backpropagate(const CuMatrix<BaseFloat>& globerr) { Backpropagate(globerr, 0); }
 
   void ReadNetwork(const char* pSrc);
   void WriteNetwork(const char* pDst);
@@ -104,7 +104,16 @@ class CuNetwork {
   /// ... and its backward walk, top component down to the stopper: Backpropagate, ComputeGradient (`empty`: no
   /// backward pass, ZeroGradient), Submit and the apply, in the MLP step's schedule.  TrainBunch and TrainEmpty
   /// both run it, so a rank with and a rank without a bunch issue the same collective sequence.
-  void DataParallelBackward(GradExchange& exchange, size_t grows, bool empty);
+  /// skip_top: the walk starts that many components below the top (BlockSoftmaxObjective has dealt with them).
+  void DataParallelBackward(GradExchange& exchange, size_t grows, bool empty, size_t skip_top = 0);
+  /// the backward walk starting skip_top components below the top, globerr being that component's error input
+  void Backpropagate(const CuMatrix<BaseFloat>& globerr, size_t skip_top);
+  /// The generic step's objective when a <blocksoftmax> is the top component, the objective cross-entropy and
+  /// the targets class ids: propagates to the component below, makes the one fused call (output into the
+  /// component, masked error into mGlobErr) and wires mGlobErr in as the error input of the component below.
+  /// false: not that case, nothing done.  RestoreTopWiring undoes the wiring after the backward walk.
+  bool BlockSoftmaxObjective(const CuMatrix<BaseFloat>& X, const CuVector<int>& labels, CuObjectiveFunction& obj);
+  void RestoreTopWiring();
 
   LayeredType mNetComponents;
   std::string mTempBasisDir;

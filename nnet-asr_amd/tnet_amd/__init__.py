@@ -301,6 +301,22 @@ class Network:
                 raise ValueError("set_discrete_params: shape mismatch")
             check(lib().tnet_net_discrete_set(self.h, i, 0, None, b.ctypes.data), "discrete_set")
 
+    def blocksoftmax_dims(self, i: int):
+        """The block widths [d_0, ...] of a <blocksoftmax> component."""
+        n = lib().tnet_net_blocksoftmax_dims(self.h, i, None, 0)
+        check(min(n, 0), "blocksoftmax_dims")
+        dims = np.zeros(n, np.int32)
+        check(min(lib().tnet_net_blocksoftmax_dims(self.h, i, dims.ctypes.data, n), 0), "blocksoftmax_dims")
+        return [int(d) for d in dims]
+
+    def blocksoftmax_invalid(self, i: int, reset: bool = False) -> int:
+        """How many (row, block) error sums the component's backward pass has met that were neither about 0 (the
+        target's block) nor about 1 (an inactive block) -- the reference's "Invalid sum" error; such a block's error
+        is zeroed.  Only dense targets or a caller's own error can produce one.  reset: clear the counter."""
+        n = C.c_long()
+        check(lib().tnet_net_blocksoftmax_invalid(self.h, i, C.byref(n), int(reset)), "blocksoftmax_invalid")
+        return int(n.value)
+
     def set_l1(self, l1: float) -> None:
         """CuNetwork::SetL1 (TNetCu --L1): the L1 constant of every <sparselinearity> component."""
         check(lib().tnet_net_set_l1(self.h, l1), "set_l1")

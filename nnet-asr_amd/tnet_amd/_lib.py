@@ -137,6 +137,9 @@ _SIGS = {
     "tnet_softmax_xent_dense": (i32, [vp, MatrixDim, vp, i32, vp, i32, vp, i32, vp, vp]),
     "tnet_mse": (i32, [vp, MatrixDim, vp, i32, vp, i32, vp, vp]),
     "tnet_stats_fetch": (i32, [vp, dp, dp, vp]),
+    "tnetF_block_softmax": (i32, [vp, vp, MatrixDim, vp, i32, vp]),
+    "tnet_block_softmax_xent": (i32, [vp, MatrixDim, vp, i32, vp, vp, i32, vp, i32, vp, vp]),
+    "tnet_block_softmax_bwd": (i32, [vp, MatrixDim, vp, i32, vp, i32, vp, vp]),
     # tnet_train.h
     "tnet_last_error": (C.c_char_p, []),
     "tnet_device_count": (i32, [C.POINTER(i32)]),
@@ -240,6 +243,8 @@ _SIGS = {
     "tnet_net_sparse_set": (i32, [vp, i32, vp, vp, vp]),
     "tnet_net_sparse_thresholds": (i32, [vp, i32, f32, f32]),
     "tnet_net_sparse_update_mask": (i32, [vp, i32]),
+    "tnet_net_blocksoftmax_dims": (i32, [vp, i32, vp, i32]),
+    "tnet_net_blocksoftmax_invalid": (i32, [vp, i32, C.POINTER(i64), i32]),
     "tnet_rnn_trainer_create": (vp, [vp, vp, i32, i32]),
     "tnet_rnn_trainer_free": (i32, [vp]),
     "tnet_rnn_trainer_utterance": (i32, [vp, vp, i32, i32, i32, vp]),

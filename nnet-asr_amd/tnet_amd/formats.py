@@ -140,7 +140,21 @@ def _write_frontend(out, L: Layer, precision: int) -> None:
         fvec(L.b)
     elif L.tag == "<window>":
         fvec(L.extra["window"])
+    elif L.tag == "<blocksoftmax>":                        # Activation.cc:73-75: the block widths
+        ivec(_check_blocksoftmax_dims(L.extra["dims"], L.n_out))
     # <sigmoid>, <softmax>, <log>: no payload
+
+
+def _check_blocksoftmax_dims(dims, n_out: int) -> np.ndarray:
+    """The block widths of a <blocksoftmax>, refused as BlockSoftmax::ReadFromStream refuses them
+    (Activation.cc:55-71) -- and when a width is not positive."""
+    dims = np.asarray(dims, dtype=np.int64).reshape(-1)
+    if dims.size == 0 or (dims <= 0).any():
+        raise ValueError(f"<blocksoftmax>: non-positive or missing block dimension in {dims.tolist()}")
+    if int(dims.sum()) != int(n_out):
+        raise ValueError("Non-matching dimension of sum of softmaxes,"
+                         f" the sum:{int(dims.sum())} GetNOutputs:{int(n_out)}")
+    return dims
 
 
 def _tokens(text: str):
@@ -287,6 +301,13 @@ def read_nnet(path_or_text: str) -> List[Layer]:
                 L.b = read_vector()
             elif tag == "<window>":
                 L.extra["window"] = read_vector()
+            elif tag == "<blocksoftmax>":
+                if i >= len(toks) or toks[i] != "v":
+                    raise ValueError("<blocksoftmax>: missing block dimensions")
+                n = int(toks[i + 1])
+                dims = [int(t) for t in toks[i + 2:i + 2 + n]]
+                i += 2 + n
+                L.extra["dims"] = [int(d) for d in _check_blocksoftmax_dims(dims, n_out)]
             layers.append(L)
         return layers
 
@@ -397,6 +418,21 @@ def gen_sparse_init(n_in: int, n_out: int, seed: int, density: float = 1.0, gaus
         extra["mask"] = mask
     return [Layer("<sparselinearity>", n_out, n_in, W, b, extra),
             Layer("<sigmoid>", n_out, n_out)]
+
+
+def gen_blocksoftmax_top(n_in: int, dims: Sequence[int], seed: int, gauss: bool = True) -> List[Layer]:
+    """The output layer of a multi-task net: one <biasedlinearity> n_in -> sum(dims) drawn as gen_mlp_init draws
+    its output layer (W^T ~ 0.1 N(0,1) with --gauss, else U[-0.1, 0.1]; zero bias) followed by a <blocksoftmax> of
+    len(dims) blocks, block j dims[j] columns wide (extra["dims"])."""
+    n_out = int(sum(int(d) for d in dims))
+    dims = [int(d) for d in _check_blocksoftmax_dims(dims, n_out)]
+    rng = np.random.default_rng(seed)
+    if gauss:
+        Wt = (0.1 * rng.standard_normal((n_out, n_in))).astype(np.float32)
+    else:
+        Wt = (rng.random((n_out, n_in)) / 5.0 - 0.1).astype(np.float32)
+    return [Layer("<biasedlinearity>", n_out, n_in, np.ascontiguousarray(Wt.T), np.zeros(n_out, np.float32)),
+            Layer("<blocksoftmax>", n_out, n_out, extra={"dims": dims})]
 
 
 def gen_recurrent_init(n_in: int, n_hid: int, n_out: int, seed: int, gauss: bool = True,
