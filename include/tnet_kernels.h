@@ -91,6 +91,29 @@ int tnetF_log_elem(float* mat, TnetMatrixDim d, void* stream);
 long tnet_col_sum_workspace(TnetMatrixDim d);
 int tnetF_add_col_sum(float alpha, const float* mat, float beta, float* vec, TnetMatrixDim d, void* workspace,
                       void* stream);
+/* Per-column first and second moments accumulated over many matrices in fp64 on the device -- the statistics loop
+ * of TNormCu (TNormCu.cc:262-282) without the copy back:
+ *   first[j] += sum_i (double)X[i,j] ;  second[j] += sum_i (double)(X[i,j] * X[i,j])
+ * the product an fp32 multiply rounded to fp32 before it is widened (TNormCu.cc:266 squares in BaseFloat).
+ *   tnet_col_moments_words(cols): doubles in an accumulator for `cols` columns (TNET_COL_MOMENTS_SLOTS slots of
+ *     2 * cols partial sums and one tag word; the layout is the kernel's).  The caller zeroes it once (tnet_memset);
+ *     8-byte aligned.
+ *   tnet_col_moments: adds X [rows x cols] (any stride >= cols, base 4-byte aligned; 16-byte loads where cols and
+ *     the stride are multiples of 4 and the base is 16-byte aligned, scalar loads otherwise; rows == 0: no-op).  Rows
+ *     are cut into slabs of TNET_COL_MOMENTS_ROWS; slab s goes to slot s % SLOTS, whose words have one writer per
+ *     launch (plain load / add / store): no floating-point atomics, and the same sequence of calls (same shapes, same
+ *     load form) gives the same bits every run.  AN ACCUMULATOR BELONGS TO ONE STREAM: launches into it must be
+ *     ordered.  A launch that meets an x or an fp32 square x*x that is not finite (a square can be infinite while x
+ *     is finite, e.g. 1e20f) records `tag` (>= 0): the accumulator keeps the smallest such tag.  Infinite inputs are
+ *     data, not faults; the sums of such an accumulator are non-finite in the affected column, otherwise unspecified.
+ *   tnet_col_moments_fetch: adds the slots in index order (one small kernel), copies first / second [cols] to the
+ *     host and sets *bad_tag to the smallest recorded tag, -1 for none; waits for the stream.  Any output may be
+ *     NULL. */
+#define TNET_COL_MOMENTS_ROWS 16
+#define TNET_COL_MOMENTS_SLOTS 64
+long tnet_col_moments_words(int cols);
+int tnet_col_moments(const float* X, TnetMatrixDim d, double* acc, int tag, void* stream);
+int tnet_col_moments_fetch(const double* acc, int cols, double* first, double* second, int* bad_tag, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Activations / objective  (cukernels.h:38-41, 51-52)

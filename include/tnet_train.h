@@ -176,6 +176,44 @@ int tnet_mlf_lookup(const char* const* patterns, int n_patterns, const char* con
  * TNetCu's CheckData error (TNetCu.cc:386), as the reference driver does. */
 long tnet_trainer_add_reader(TnetTrainer* t, TnetFeatureReader* r, long max_utts);
 
+/* ---- global mean / variance normalisation: the TNormCu loop (src/TNormCu.cc:215-343) ----------
+ * Per utterance: upload, propagate through `transform` (borrowed, may be NULL: then `dim` is the feature
+ * dimension; with a transform the dimension is its output dimension and `dim` is ignored), and add the rows
+ * between the start_ext / end_ext context rows into per-column fp64 sums of x and of the fp32 square x*x on the
+ * device (tnet_col_moments: no trimmed copy, no copy back, nothing synchronised per utterance).  finish:
+ *   mean = first / N, var = second / N - mean^2, <bias> = -mean, <window> = 1 / sqrt(var)      (in double)
+ * -- a zero or negative variance gives inf / nan as in the reference, no clamp.
+ * The frame-count quirk: TNormCu.cc:286 adds feats_host.Rows() -- the rows INCLUDING the context frames -- to N,
+ * while the sums cover only the trimmed rows (examples/01 at +-25 frames: N = 60,457 for 55,457 summed frames, a
+ * "mean" 0.917 of the true one).  Existing transforms were made this way: count_ext_frames != 0 reproduces it,
+ * 0 divides by the rows that were summed.
+ *   add_utterance : feats [rows_ext x cols] (host, ld) including the context rows; rows_ext < start_ext + end_ext + 1
+ *                   is refused.  The utterance's index (0, 1, ...) is its tag.
+ *   add_reader    : up to max_utts utterances (< 0: the rest of the list) from a reader created with the same
+ *                   start_ext / end_ext; returns the frames summed (< 0: error)
+ *   merge         : first, second and N summed over the ranks of `comm` (one all-reduce of 2 dim + 1 doubles);
+ *                   only before finish.  A rank whose data made an accumulator NaN / Inf fails before the collective.
+ *   finish        : one device fetch, then the vectors.  An utterance holding a value whose fp32 square is not finite
+ *                   makes it fail with "nan/inf in accumulators" naming the first such utterance (index, and the
+ *                   logical name when it came from a reader).
+ *   stats         : first / second [dim] and N so far (fetches; no utterance can be added afterwards)
+ *   vectors       : bias / window [dim] as doubles (after finish)
+ *   write         : TNormCu's file (TNormCu.cc:320-327): "<bias> D D\n" + vector + "\n\n<window> D D\n" + vector +
+ *                   "\n\n", the vectors as KaldiLib writes a Vector<double> ("v D  x x ... ", 6 significant digits of
+ *                   the double)
+ *   report        : "frames: N, max_bias: b, max_window: w, min_window: w\n" (TNormCu.cc:337-341) */
+typedef struct TnetNorm TnetNorm;
+TnetNorm* tnet_norm_create(TnetNetwork* transform, int dim, int start_ext, int end_ext, int count_ext_frames);
+int tnet_norm_add_utterance(TnetNorm* n, const float* feats, int rows_ext, int cols, int ld);
+long tnet_norm_add_reader(TnetNorm* n, TnetFeatureReader* r, long max_utts);
+int tnet_norm_merge(TnetNorm* n, TnetComm* comm);
+int tnet_norm_finish(TnetNorm* n);
+int tnet_norm_stats(TnetNorm* n, double* first, double* second, long* frames);
+int tnet_norm_vectors(TnetNorm* n, double* bias, double* window);
+int tnet_norm_write(TnetNorm* n, const char* path);
+int tnet_norm_report(TnetNorm* n, char* buf, int cap);
+int tnet_norm_free(TnetNorm* n);
+
 /* ---- RBM pre-training (CuRbm, cuRbm.cc; the TRbmCu loop, TRbmCu.cc:291-357) ----------------
  * <rbm> parameters: W [n_vis x n_hid] (host row-major), visible / hidden biases; types[0..1] =
  * visible / hidden unit type (0 Bernoulli, 1 Gaussian; -1 in set = keep). */

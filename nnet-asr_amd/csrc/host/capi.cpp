@@ -9,6 +9,7 @@
 #include "curbm.h"
 #include "curecurrent.h"
 #include "cudiscrete.h"
+#include "cunorm.h"
 #include "cushared.h"
 #include "cusparse.h"
 #include "htkio.h"
@@ -55,6 +56,9 @@ struct TnetRnnTrainer {
 struct TnetFeatureReader {
   std::unique_ptr<tnetio::FeatureReader> r;
   int start_ext = 0, end_ext = 0;
+};
+struct TnetNorm {
+  std::unique_ptr<CuNormAccumulator> a;
 };
 struct TnetComm {
   std::unique_ptr<GradExchange> ex;
@@ -550,6 +554,75 @@ long tnet_trainer_add_reader(TnetTrainer* t, TnetFeatureReader* r, long max_utts
     g_last_error = e.what();
     return TNET_ERR_RUNTIME;
   }
+}
+
+// ------------------------------------------------------------------------- normalisation pass
+TnetNorm* tnet_norm_create(TnetNetwork* transform, int dim, int start_ext, int end_ext, int count_ext_frames) {
+  try {
+    if (start_ext < 0 || end_ext < 0) Error("tnet_norm_create: negative frame extension");
+    if (!transform && dim <= 0) Error("tnet_norm_create: without a transform the feature dimension is required");
+    std::unique_ptr<TnetNorm> h(new TnetNorm);
+    h->a.reset(new CuNormAccumulator(transform ? &transform->net : nullptr, (size_t)(dim > 0 ? dim : 0),
+                                     (size_t)start_ext, (size_t)end_ext, count_ext_frames != 0));
+    return h.release();
+  }
+  TRY_END_PTR
+}
+int tnet_norm_add_utterance(TnetNorm* n, const float* feats, int rows_ext, int cols, int ld) {
+  TRY_BEGIN if (!n) Error("tnet_norm_add_utterance: null handle");
+  if (rows_ext < 0 || cols < 0 || ld < 0) Error("tnet_norm_add_utterance: negative dimension");
+  n->a->AddUtterance(feats, (size_t)rows_ext, (size_t)cols, (size_t)ld);
+  TRY_END
+}
+long tnet_norm_add_reader(TnetNorm* n, TnetFeatureReader* r, long max_utts) {
+  try {
+    if (!n || !r) Error("tnet_norm_add_reader: null handle");
+    return n->a->AddReader(*r->r, (size_t)r->start_ext, (size_t)r->end_ext, max_utts);
+  } catch (std::exception& e) {
+    g_last_error = e.what();
+    return TNET_ERR_RUNTIME;
+  }
+}
+int tnet_norm_merge(TnetNorm* n, TnetComm* c) {
+  TRY_BEGIN if (!n || !c) Error("tnet_norm_merge: null handle");
+  n->a->Merge(*c->ex);
+  TRY_END
+}
+int tnet_norm_finish(TnetNorm* n) {
+  TRY_BEGIN if (!n) Error("tnet_norm_finish: null handle");
+  n->a->Finish();
+  TRY_END
+}
+int tnet_norm_stats(TnetNorm* n, double* first, double* second, long* frames) {
+  TRY_BEGIN if (!n) Error("tnet_norm_stats: null handle");
+  const size_t D = n->a->Dim();
+  if (first) std::memcpy(first, n->a->First().data(), D * sizeof(double));
+  if (second) std::memcpy(second, n->a->Second().data(), D * sizeof(double));
+  if (frames) *frames = (long)n->a->Frames();
+  TRY_END
+}
+int tnet_norm_vectors(TnetNorm* n, double* bias, double* window) {
+  TRY_BEGIN if (!n) Error("tnet_norm_vectors: null handle");
+  const size_t D = n->a->Dim();
+  if (bias) std::memcpy(bias, n->a->Bias().data(), D * sizeof(double));
+  if (window) std::memcpy(window, n->a->Window().data(), D * sizeof(double));
+  TRY_END
+}
+int tnet_norm_write(TnetNorm* n, const char* path) {
+  TRY_BEGIN if (!n || !path) Error("tnet_norm_write: null argument");
+  n->a->Write(path);
+  TRY_END
+}
+int tnet_norm_report(TnetNorm* n, char* buf, int cap) {
+  TRY_BEGIN if (!n || !buf || cap <= 0) Error("tnet_norm_report: bad arguments");
+  const std::string s = n->a->Report();
+  std::strncpy(buf, s.c_str(), (size_t)cap - 1);
+  buf[cap - 1] = 0;
+  TRY_END
+}
+int tnet_norm_free(TnetNorm* n) {
+  TRY_BEGIN delete n;
+  TRY_END
 }
 
 // ------------------------------------------------------------------------------------ RBM

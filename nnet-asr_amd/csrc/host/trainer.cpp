@@ -685,13 +685,16 @@ void RcclExchange::WaitAll() {
 void RcclExchange::AllReduceHost(double* v, int n) {
   CuDevice::Instantiate().KTCloseRun();  // no roofline timing run spans an exchange step
   if (n <= 0) return;
-  if (n > 512) Error("RcclExchange::AllReduceHost: too many values");
   CuDevice& dev = CuDevice::Instantiate();
   TNET_HIP_CALL(hipStreamSynchronize(dev.Stream()));
-  TNET_HIP_CALL(hipMemcpyAsync(mImpl->dscratch, v, n * sizeof(double), hipMemcpyHostToDevice, mImpl->comm_stream));
-  NCCL_CALL(ncclAllReduce(mImpl->dscratch, mImpl->dscratch, n, ncclDouble, ncclSum, mImpl->comm, mImpl->comm_stream));
-  TNET_HIP_CALL(hipMemcpyAsync(v, mImpl->dscratch, n * sizeof(double), hipMemcpyDeviceToHost, mImpl->comm_stream));
-  TNET_HIP_CALL(hipStreamSynchronize(mImpl->comm_stream));
+  // the scratch buffer holds 512 doubles: a longer vector (the normalisation statistics, 2 dim + 1) goes in pieces
+  for (int o = 0; o < n; o += 512) {
+    const int m = n - o < 512 ? n - o : 512;
+    TNET_HIP_CALL(hipMemcpyAsync(mImpl->dscratch, v + o, m * sizeof(double), hipMemcpyHostToDevice, mImpl->comm_stream));
+    NCCL_CALL(ncclAllReduce(mImpl->dscratch, mImpl->dscratch, m, ncclDouble, ncclSum, mImpl->comm, mImpl->comm_stream));
+    TNET_HIP_CALL(hipMemcpyAsync(v + o, mImpl->dscratch, m * sizeof(double), hipMemcpyDeviceToHost, mImpl->comm_stream));
+    TNET_HIP_CALL(hipStreamSynchronize(mImpl->comm_stream));
+  }
 }
 
 void RcclExchange::AllReduceDevice(float* buf, size_t n) {

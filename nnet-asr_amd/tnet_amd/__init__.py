@@ -16,6 +16,7 @@ from . import formats  # noqa: F401  (host formats; no device code)
 from ._lib import HOST_ALLREDUCE_FN, LIB_PATH, MatrixDim, TnetError, check, check_ptr, header_symbols, lib
 
 __all__ = ["DeviceArray", "Network", "Objective", "Trainer", "RbmTrainer", "RnnTrainer", "Comm", "TnetError", "synchronize",
+           "Normalizer",
            "FeatureReader", "htk_read", "mask_match", "mlf_lookup",
            "pad_stride",
            "device_count", "version", "LIB_PATH", "header_symbols", "formats"]
@@ -587,6 +588,91 @@ class RnnTrainer:
         try:
             if getattr(self, "h", None):
                 lib().tnet_rnn_trainer_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+class Normalizer:
+    """The TNormCu pass (src/TNormCu.cc:215-343): global mean / variance normalisation of a feature transform's
+    output, the <bias> + <window> pair every recipe appends to its transform.  The per-column sums of x and of the
+    fp32 square x*x stay on the device in fp64 (tnet_col_moments); nothing is copied back per utterance.
+
+    transform: a front-end Network (None: the features themselves, then `dim` is their dimension).  Utterances
+    carry start_ext / end_ext context rows, which are propagated and then left out of the sums.
+
+    count_ext_frames: the reference divides by the frame count INCLUDING the context rows (TNormCu.cc:286) while
+    the sums cover only the trimmed rows -- on examples/01 at +-25 frames N = 60,457 for 55,457 summed frames, a
+    "mean" 0.917 of the true one.  Existing transforms were made this way, so True (the default) reproduces it;
+    False divides by the rows that were summed."""
+
+    def __init__(self, transform: Optional[Network] = None, dim: Optional[int] = None, start_ext: int = 0,
+                 end_ext: int = 0, count_ext_frames: bool = True):
+        if transform is None and dim is None:
+            raise ValueError("Normalizer: a transform or the feature dimension is required")
+        self._transform = transform   # borrowed by the C++ accumulator: keep it alive
+        self.dim = int(transform.n_out) if transform is not None and transform.components() else int(dim)
+        self.start_ext, self.end_ext, self.count_ext_frames = int(start_ext), int(end_ext), bool(count_ext_frames)
+        self.h = check_ptr(lib().tnet_norm_create(transform.h if transform is not None else None, self.dim,
+                                                  self.start_ext, self.end_ext, int(self.count_ext_frames)),
+                           "tnet_norm_create")
+
+    def add(self, feats: np.ndarray) -> None:
+        """one utterance [rows incl. the context rows x dim]"""
+        feats, _ = _utterance(feats, None, "Normalizer.add")
+        check(lib().tnet_norm_add_utterance(self.h, feats.ctypes.data, feats.shape[0], feats.shape[1],
+                                            feats.shape[1]), "norm add")
+
+    def add_reader(self, reader: "FeatureReader", max_utts: int = -1) -> int:
+        """the TNormCu main loop over a native FeatureReader (same start_ext / end_ext); returns the frames summed"""
+        n = lib().tnet_norm_add_reader(self.h, reader.h, max_utts)
+        if n < 0:
+            check(int(n), "norm add_reader")
+        return int(n)
+
+    def merge(self, comm: "Comm") -> None:
+        """sum the statistics over the ranks of `comm` (before finish); every rank then holds the corpus's"""
+        check(lib().tnet_norm_merge(self.h, comm.h), "norm merge")
+
+    def finish(self) -> None:
+        check(lib().tnet_norm_finish(self.h), "norm finish")
+
+    def stats(self):
+        """(first [dim], second [dim], N): float64 sums of x and of the fp32 squares, and the divisor"""
+        first, second = np.empty(self.dim, np.float64), np.empty(self.dim, np.float64)
+        n = C.c_long()
+        check(lib().tnet_norm_stats(self.h, first.ctypes.data, second.ctypes.data, C.byref(n)), "norm stats")
+        return first, second, int(n.value)
+
+    def vectors(self):
+        """(bias, window) as float64, after finish()"""
+        bias, window = np.empty(self.dim, np.float64), np.empty(self.dim, np.float64)
+        check(lib().tnet_norm_vectors(self.h, bias.ctypes.data, window.ctypes.data), "norm vectors")
+        return bias, window
+
+    def bad_window_entries(self) -> int:
+        """inf / nan entries of <window> (columns of zero or negative variance; not clamped, as the reference)"""
+        return int(np.count_nonzero(~np.isfinite(self.vectors()[1])))
+
+    def layers(self):
+        """[<bias>, <window>] as formats.Layer (float32, as a network holds them)"""
+        bias, window = self.vectors()
+        return [formats.Layer("<bias>", self.dim, self.dim, b=bias.astype(np.float32)),
+                formats.Layer("<window>", self.dim, self.dim, extra={"window": window.astype(np.float32)})]
+
+    def write(self, path: str) -> None:
+        """TNormCu's --TARGETMMF file (6 significant digits of the doubles)"""
+        check(lib().tnet_norm_write(self.h, path.encode()), "norm write")
+
+    def report(self) -> str:
+        buf = C.create_string_buffer(512)
+        check(lib().tnet_norm_report(self.h, buf, 512), "norm report")
+        return buf.value.decode()
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().tnet_norm_free(self.h)
                 self.h = None
         except Exception:
             pass

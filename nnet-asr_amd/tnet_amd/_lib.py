@@ -53,6 +53,9 @@ _SIGS = {
     "tnetF_log_elem": (i32, [vp, MatrixDim, vp]),
     "tnet_col_sum_workspace": (i64, [MatrixDim]),
     "tnetF_add_col_sum": (i32, [f32, vp, f32, vp, MatrixDim, vp, vp]),
+    "tnet_col_moments_words": (i64, [i32]),
+    "tnet_col_moments": (i32, [vp, MatrixDim, vp, i32, vp]),
+    "tnet_col_moments_fetch": (i32, [vp, i32, vp, vp, C.POINTER(i32), vp]),
     "tnetF_sigmoid": (i32, [vp, vp, MatrixDim, vp]),
     "tnetF_diff_sigmoid": (i32, [vp, vp, vp, MatrixDim, vp]),
     "tnetF_softmax": (i32, [vp, vp, MatrixDim, vp]),
@@ -209,6 +212,16 @@ _SIGS = {
     "tnet_mask_match": (i32, [C.c_char_p, C.c_char_p, C.c_char_p, i32]),
     "tnet_mlf_lookup": (i32, [vp, i32, vp, i32, vp]),
     "tnet_trainer_add_reader": (i64, [vp, vp, i64]),
+    "tnet_norm_create": (vp, [vp, i32, i32, i32, i32]),
+    "tnet_norm_add_utterance": (i32, [vp, vp, i32, i32, i32]),
+    "tnet_norm_add_reader": (i64, [vp, vp, i64]),
+    "tnet_norm_merge": (i32, [vp, vp]),
+    "tnet_norm_finish": (i32, [vp]),
+    "tnet_norm_stats": (i32, [vp, vp, vp, C.POINTER(i64)]),
+    "tnet_norm_vectors": (i32, [vp, vp, vp]),
+    "tnet_norm_write": (i32, [vp, C.c_char_p]),
+    "tnet_norm_report": (i32, [vp, C.c_char_p, i32]),
+    "tnet_norm_free": (i32, [vp]),
     "tnet_comm_unique_id": (i32, [C.c_char_p]),
     "tnet_comm_create": (vp, [i32, i32, C.c_char_p]),
     "tnet_comm_free": (i32, [vp]),
@@ -290,6 +303,16 @@ _SIGS = {
 
 # int fn(void* user, void* buf, long n, int is_double) -- tnet_host_allreduce_fn
 HOST_ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_long, C.c_int)
+
+
+def header_constant(name: str) -> int:
+    """An integer #define of include/tnet_kernels.h (e.g. TNET_COL_MOMENTS_ROWS): kernel geometry the tests and
+    tools size their cases by instead of guessing it."""
+    text = open(os.path.join(INCLUDE_DIR, "tnet_kernels.h")).read()
+    m = re.search(r"^#define\s+%s\s+(\d+)\s*$" % re.escape(name), text, flags=re.M)
+    if not m:
+        raise KeyError(name)
+    return int(m.group(1))
 
 
 def header_symbols():
