@@ -17,6 +17,10 @@
  *   - no entry point reads a value from, or writes, anything outside [rows x cols] of an operand unless its own
  *     comment says so, and padding contents are unspecified (tests/test_gpu_views.py for the dense family,
  *     tests/test_gpu_rnn_views.py for the single-frame chain, tests/test_gpu_rbm_views.py for the RBM step);
+ *   - non-finite inputs are data: an output is non-finite exactly where IEEE arithmetic on the entry point's
+ *     stated formula makes it so (one row, column, slab sum, block or element -- never a neighbour reached
+ *     through a clamped re-read, a fused sum or a pair launch's other half), and a cross-entropy over a NaN
+ *     posterior is NaN, the clamp being the reference's `v < FLT_MIN ? FLT_MIN : v` (tests/test_gpu_nonfinite.py);
  *   - launch geometry is a kernel-internal detail (no dim3 in the ABI, unlike cukernels.h);
  *   - every launch goes on the caller's stream (hipStream_t passed as void*; NULL = default);
  *     no device synchronisation inside (the reference synchronised after every call,
@@ -732,7 +736,7 @@ int tnet_add_gauss_noise(float* mat, TnetMatrixDim d, float scale, unsigned* z1,
  *  _mul_elem, _add_col_sum):
  *   y = softmax(Z row)          -> written to Y if Y != NULL
  *   E = y - onehot(label)       (label < 0: all-zero target row)
- *   xent += -log(max(y[label], FLT_MIN)), correct += #(argmax y == argmax target)
+ *   xent += -log(y[label] < FLT_MIN ? FLT_MIN : y[label]) (a NaN stays a NaN), correct += #(argmax y == argmax target)
  *   stats: device array of TNET_STATS_WORDS doubles (or NULL), accumulated without contention:
  *   workgroup w adds its rows into slot (w % TNET_STATS_SLOTS); totals are
  *   xent = sum_i stats[2i], correct = sum_i stats[2i+1] (tnet_stats_fetch).
@@ -741,7 +745,8 @@ int tnet_softmax_xent(const float* Z, TnetMatrixDim dZ, const int* labels, float
                       int strideE, double* stats, void* stream);
 /* Same objective for dense desired matrices D (any soft targets; cuObjectiveFunction.cc:50-83):
  * Y = softmax(Z) (if Z != NULL, else Y already holds the network output), E = Y - D, stats as above
- * with xent = -sum D log(max(Y, FLT_MIN)). */
+ * with xent = -sum over ALL columns of D log(Y < FLT_MIN ? FLT_MIN : Y): a NaN or +inf posterior under a zero
+ * target makes the row's cross-entropy NaN (LogElem + MulElem, 0 * NaN), and two rows without a maximum do not match. */
 int tnet_softmax_xent_dense(const float* Z, TnetMatrixDim dZ, const float* D, int strideD, float* Y,
                             int strideY, float* E, int strideE, double* stats, void* stream);
 /* Mean-square-error objective (CuMeanSquareError::Evaluate, cuObjectiveFunction.cc:28-45):
@@ -765,7 +770,7 @@ int tnetF_block_softmax(float* y, const float* x, TnetMatrixDim d, const int* of
  *   Y = block softmax(Z row)    -> written if Y != NULL
  *   E = y - onehot(label) in the label's block, +0.0f in every other block (the block found from the label
  *       in offsets; label < 0 or >= cols: an unlabeled row, its whole error +0.0f)
- *   xent += -log(max(y[label], FLT_MIN)); correct += #(argmax over the WHOLE row of y == label, column 0 for
+ *   xent += -log(y[label] < FLT_MIN ? FLT_MIN : y[label]); correct += #(argmax over the WHOLE row of y == label, column 0 for
  *   an unlabeled row) -- the reference's accounting; stats as tnet_softmax_xent.
  * With B == 1 Y, the stats and E of labelled rows are tnet_softmax_xent's bit for bit.  The same Y (and, in the
  * label's block, E) as tnetF_block_softmax -> tnet_softmax_xent(Z = NULL) -> tnet_block_softmax_bwd. */

@@ -93,7 +93,9 @@ void CuCrossEntropy::Evaluate(const CuMatrix<BaseFloat>& out, const CuMatrix<Bas
        << " Netoutput:" << out.Cols() << " Targets:" << des.Cols();
     Error(os.str());
   }
-  // err = y - d; correct += argmax match; xent += -sum d log(max(y, FLT_MIN))  (one kernel)
+  // err = y - d; correct += argmax match; xent += -sum over ALL columns of d log(y < FLT_MIN ? FLT_MIN : y) -- the
+  // reference's clamp (cukernels.cu:131-141), which keeps a NaN, and its LogElem + MulElem: a NaN or +inf posterior
+  // under a zero target is NaN too  (one kernel)
   err.Init(out.Rows(), out.Cols());
   TnetMatrixDim d = out.Dim();
   TNET_SAFE_CALL(tnet_softmax_xent_dense(nullptr, d, des.pCUData(), (int)des.Stride(), const_cast<float*>(out.pCUData()),

@@ -2196,7 +2196,7 @@ __global__ __launch_bounds__(kSxThreads) void affine_softmax_xent_kernel(
       }
     ay = wave_argmax(ay);
     if (lane == 0) {
-      if (t >= 0) wx += -(double)logf(fmaxf(fast_exp(zt - m) * rsum, FLT_MIN));
+      if (t >= 0) wx += -(double)logf(clamp_flt_min(fast_exp(zt - m) * rsum));
       wc += ay.i == (t >= 0 ? t : 0) ? 1.0 : 0.0;
     }
   }

@@ -317,7 +317,7 @@ __global__ __launch_bounds__(256) void gemv_softmax_xent_final(const float* __re
     ArgMax a = sarg[0];
 #pragma unroll
     for (int w = 1; w < 4; ++w) a = argmax_merge(a, sarg[w]);
-    const double xent = (t >= 0 && t < N) ? -(double)logf(fmaxf(syt, FLT_MIN)) : 0.0;
+    const double xent = (t >= 0 && t < N) ? -(double)logf(clamp_flt_min(syt)) : 0.0;
     atomicAdd(stats, xent);
     atomicAdd(stats + 1, (a.i == (t >= 0 ? t : 0)) ? 1.0 : 0.0);
   }
@@ -812,7 +812,7 @@ __global__ __launch_bounds__(256) void rnn_out_bwd_kernel(
       ay.i = j;
       if (yout) yout[j] = yj;
       if (eout) eout[j] = ej;
-      if (j == t && stats) atomicAdd(stats, -(double)logf(fmaxf(yj, FLT_MIN)));
+      if (j == t && stats) atomicAdd(stats, -(double)logf(clamp_flt_min(yj)));
       if (train) {
         float g = ej;
         if (cb) {

@@ -1,5 +1,6 @@
 // kcommon.h -- shared device-side helpers for the gfx950 kernels of the TNet SGD path.
 #pragma once
+#include <float.h>
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -174,6 +175,11 @@ __device__ __forceinline__ float fast_exp(float x) { return (float)exp((double)x
 #else
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(1.44269504088896341f * x); }
 #endif
+
+// the clamp in front of every cross-entropy's log, in the reference's form (_log_elem, cukernels.cu:131-141:
+// `if (v < FLT_MIN) v = FLT_MIN`).  A NaN fails the comparison and stays a NaN, so the cross-entropy over a NaN
+// posterior is NaN as in the reference; fmaxf(NaN, FLT_MIN) is FLT_MIN and would report a finite 87.34
+__device__ __forceinline__ float clamp_flt_min(float v) { return v < FLT_MIN ? FLT_MIN : v; }
 
 inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 

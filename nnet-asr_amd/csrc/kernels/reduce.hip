@@ -166,6 +166,7 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
   ArgMax ay{-1e20f, 0x7fffffff}, ad{-1e20f, 0x7fffffff};
   double xent = 0.0;
   float ytl = 0.f;  // KIND 0: the y written for column t, on the lane that owns t
+  bool ynan = false;  // KIND 1: this lane saw a posterior whose log is not finite
   float* yrow = Y ? Y + (long)row * strideY : nullptr;
   float* erow = E ? E + (long)row * strideE : nullptr;
   const float* drow = (KIND == 1) ? D + (long)row * strideD : nullptr;
@@ -179,7 +180,12 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     }
     if (y > ay.v) { ay.v = y; ay.i = c; }
     if (KIND == 1 && dv > ad.v) { ad.v = dv; ad.i = c; }
-    if (KIND == 1 && dv != 0.f) xent -= (double)dv * (double)logf(fmaxf(y, FLT_MIN));
+    // the reference sums d * log(y) over every column (LogElem + MulElem): a NaN or +inf posterior under a zero
+    // target is 0 * NaN / 0 * inf = NaN there.  One comparison instead of a logf per skipped element
+    if (KIND == 1) {
+      if (dv != 0.f) xent -= (double)dv * (double)logf(clamp_flt_min(y));
+      else ynan |= !(y <= FLT_MAX);
+    }
     return dv;
   };
   if (cached) {
@@ -213,15 +219,17 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
     ad = wave_argmax(ad);
     des = ad.i;
   }
-  if (KIND == 1) xent = wave_sum_d(xent);
+  if (KIND == 1) xent = wave_sum_d(ynan ? (double)NAN : xent);
   // the label column's y from its owner lane's registers (the value a re-read of the row recomputes:
   // fast_exp(z_t - m) * rsum, or y_t itself) -- no dependent load at the row's end
   float yt = 0.f;
   if (KIND == 0) yt = __shfl(ytl, t < 0 ? 0 : cached ? (t & 255) >> 2 : t & 63, 64);
   if (lane == 0) {
-    if (KIND == 0 && t >= 0) xent = -(double)logf(fmaxf(yt, FLT_MIN));
+    if (KIND == 0 && t >= 0) xent = -(double)logf(clamp_flt_min(yt));
     red[0][wv] = xent;
-    red[1][wv] = (ay.i == des) ? 1.0 : 0.0;
+    // (no maximum on either side -- a row of NaN in Y and in D -- is no match: _check_class's ids -1 / -2; with
+    // class-id labels des is a column, never the empty id)
+    red[1][wv] = (ay.i == des && ay.i != 0x7fffffff) ? 1.0 : 0.0;
   }
   __syncthreads();
   if (threadIdx.x == 0 && stats) {
@@ -266,7 +274,9 @@ __global__ __launch_bounds__(256) void check_class_kernel(const float* __restric
   }
   a = wave_argmax(a);
   b = wave_argmax(b);
-  if (lane == 0) match[row] = (a.i == b.i) ? 1 : 0;
+  // a row with nothing above -1e20 (all NaN, say) has no maximum: the reference starts from out_id = -1 and
+  // des_id = -2 (cukernels.cu:405), so two such rows do not match
+  if (lane == 0) match[row] = (a.i == b.i && a.i != 0x7fffffff) ? 1 : 0;
 }
 
 }  // namespace tnetk
@@ -404,7 +414,7 @@ __device__ __forceinline__ void softmax_xent_row4(const float* __restrict__ Z, T
     for (int w = 1; w < 4; ++w) a = argmax_merge(a, sarg[w]);
     const int des = t >= 0 ? t : 0;  // all-zero target row: first max of zeros is column 0
     double xent = 0.0;
-    if (t >= 0) xent = -(double)logf(fmaxf(syt, FLT_MIN));
+    if (t >= 0) xent = -(double)logf(clamp_flt_min(syt));
     if (stats) {
       const int slot = row % TNET_STATS_SLOTS;
       atomicAdd(stats + 2 * slot, xent);

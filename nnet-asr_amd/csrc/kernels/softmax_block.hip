@@ -190,7 +190,7 @@ __global__ __launch_bounds__(256) void block_softmax_kernel(const float* __restr
     const int des = t >= 0 ? t : 0;  // all-zero target row: first max of zeros is column 0
     const float yt = __shfl(ytl, t < 0 ? 0 : V4 ? (t & 255) >> 2 : t & 63, 64);
     double xent = 0.0;
-    if (t >= 0) xent = -(double)logf(fmaxf(yt, FLT_MIN));
+    if (t >= 0) xent = -(double)logf(clamp_flt_min(yt));
     bs_stats(stats, quad, row, true, xent, ay.i == des);
   }
 }
@@ -247,7 +247,7 @@ __global__ __launch_bounds__(256) void block_softmax_wide_kernel(const float* __
     const int des = t >= 0 ? t : 0;
     const float yt = __shfl(ytl, tlane, 64);
     double xent = 0.0;
-    if (t >= 0) xent = -(double)logf(fmaxf(yt, FLT_MIN));
+    if (t >= 0) xent = -(double)logf(clamp_flt_min(yt));
     bs_stats(stats, false, row, true, xent, ay.i == des);
   }
 }
