@@ -134,6 +134,38 @@ int tnetF_softmax(float* y, const float* x, TnetMatrixDim d, void* stream);
 int tnetF_check_class(const float* out, const float* des, int* match, TnetMatrixDim d, void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Output stage of the forward pass  (TFeaCatCu.cc:236-265: trim, GMMBYPASS, LOGPOSTERIOR, byte order)
+ * ---------------------------------------------------------------------------------- */
+/* tnet_feacat_emit: rows of Y [dY.rows x dY.cols, any stride >= cols, base 4-byte aligned] -> file-ready words.
+ * Segment s (HOST arrays of nseg ints) takes source rows [seg_src_row[s], + seg_rows[s]) and stores f(y) of every
+ * element as dense rows of exactly C = dY.cols 32-bit words starting at word seg_dst_row[s] * C of `out` (device,
+ * 4-byte aligned): the table drops every utterance's context rows and lays its file body out as one range.
+ *   mode: TNET_FEACAT_GMMBYPASS first, y <- (float) sqrt(-2.0 * log((double) y)); then TNET_FEACAT_LOGPOSTERIOR,
+ *         y <- (float) log((double) y), on the first's fp32 result when both are set (fp64 arithmetic from the fp32
+ *         input, one rounding each: what the reference's lines compute, tests/golden/feacat_ref.npz).  Edge values
+ *         are data: 0 -> -inf (log) / +inf (bypass); 1 -> +0 (log) / -0 (bypass: sqrt(-2.0 * +0.0) = sqrt(-0.0));
+ *         negative -> NaN; NaN and +inf propagate.  mode 0 copies bits.
+ *   swap: every word stored byte-reversed (HTK files are big-endian).
+ * 16-byte loads where C and the stride are multiples of 4 and Y is 16-byte aligned; 16-byte stores on every aligned
+ * group of four output words whatever C and the destination offsets are.  Stride padding of Y is never read into the
+ * output and nothing outside the destination ranges is written.
+ * TNET_ERR_ARG before any launch: a segment outside dY, a negative entry, destination ranges that overlap, a NULL
+ * operand; TNET_ERR_UNSUPPORTED for a segment of 2^31 words or more.  nseg == 0 or no rows at all: TNET_OK, no launch.
+ * One launch per 64 segments.
+ *
+ * tnet_softmax_emit: the same from the pre-softmax activations Z -- the row softmax by the device function
+ * tnetF_softmax runs (softmax_row.h; the regime tnetF_softmax picks for an output laid out like Z: rows in registers
+ * where C % 4 == 0 <= 4096, Z 16-byte aligned and the stride a multiple of 4, re-read otherwise), mode, byte order and
+ * the dense store in one kernel, one wave per EMITTED row: the posterior matrix is never written, rows outside every
+ * segment are not computed.  Bit-identical to tnetF_softmax followed by tnet_feacat_emit. */
+#define TNET_FEACAT_GMMBYPASS 1
+#define TNET_FEACAT_LOGPOSTERIOR 2
+int tnet_feacat_emit(const float* Y, TnetMatrixDim dY, const int* seg_src_row, const int* seg_dst_row,
+                     const int* seg_rows, int nseg, int mode, int swap, void* out, void* stream);
+int tnet_softmax_emit(const float* Z, TnetMatrixDim dZ, const int* seg_src_row, const int* seg_dst_row,
+                      const int* seg_rows, int nseg, int mode, int swap, void* out, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Gathers / front-end transforms  (cukernels.h:43-45)
  * ---------------------------------------------------------------------------------- */
 /* y[i,j] = x[i + off[j / in.cols], j % in.cols] with edge clamp  -- cudaF_expand (cukernels.cu:347-361) */

@@ -214,6 +214,47 @@ int tnet_norm_write(TnetNorm* n, const char* path);
 int tnet_norm_report(TnetNorm* n, char* buf, int cap);
 int tnet_norm_free(TnetNorm* n);
 
+/* ---- the forward pass: the TFeaCatCu loop (src/TFeaCatCu.cc:215-270) ----------
+ * Turns a trained network into posterior / bottleneck feature files.  Per utterance: upload, propagate through
+ * `transform` (borrowed, may be NULL or empty) and append the rows between the start_ext / end_ext context rows to a
+ * packing buffer; per pack of pack_rows rows (0: the default, 4096; an utterance may straddle two packs) the network
+ * once and one emit kernel (tnet_softmax_emit when the last component is <softmax>, else tnet_feacat_emit): `mode`
+ * (TNET_FEACAT_GMMBYPASS | TNET_FEACAT_LOGPOSTERIOR, in that order, include/tnet_kernels.h), the byte order and the
+ * dense file layout on the device, one async copy per pack into a ring of three pinned slots.  A network with a
+ * component that mixes rows (<expand>, <recurrent>, <blockarray>, ...) is not packed: one utterance a pass, all rows
+ * through the network, the context rows dropped by the emit (stats: packed = 0); pack_rows = -1 asks for that route
+ * whatever the network (comparisons).  An empty network copies the transform's output.
+ *   create        : fails (NULL, tnet_last_error) when the transform's output dimension differs from the network's input
+ *                   dimension or the output has more than 8191 columns (the HTK sample size is an int16)
+ *   set_output    : before the first utterance.  dir or ext non-NULL: files TARGETPARAMDIR / basename(logical) .
+ *                   TARGETPARAMEXT by MakeHtkFileName's rules (Common.cc:118-172), kind USER, the input's sample period,
+ *                   swap != 0: big-endian (header and body), written by two writer threads.  Both NULL: the results
+ *                   stay in memory for fetch (the default), `swap` choosing the byte order of the kept words.
+ *   add_utterance : feats [rows incl. the context rows x cols], leading dimension ld, host memory; fails naming the
+ *                   utterance for rows <= start_ext + end_ext or a wrong dimension.  A non-finite feature is data.
+ *   add_reader    : up to max_utts (< 0: all) utterances of a reader with the same frame extension; returns the
+ *                   frames emitted, < 0 on error
+ *   finish        : the last pack, the drain, the writers; fails naming the first file that could not be written
+ *                   (every other utterance is written in full)
+ *   fetch         : memory sink, after finish: utterance `index` in the order added; 1 = delivered, 0 = no such index.
+ *                   out == NULL asks for rows / cols / sample_period / logical only; else rows * cols floats (cap)
+ *   stats         : emitted frames, utterances, network passes ("packs") so far, and whether the pass packs
+ * tnet_htk_write  : host only, no device: one uncompressed HTK file (12-byte header + rows * cols floats), swap != 0:
+ *                   big-endian.  Fails for cols > 8191 or a file that cannot be written (removed if partial). */
+typedef struct TnetFeaCat TnetFeaCat;
+TnetFeaCat* tnet_feacat_create(TnetNetwork* net, TnetNetwork* transform, int start_ext, int end_ext, int mode,
+                               int pack_rows);
+int tnet_feacat_set_output(TnetFeaCat* f, const char* dir, const char* ext, int swap);
+int tnet_feacat_add_utterance(TnetFeaCat* f, const float* feats, int rows, int cols, int ld, const char* logical_name,
+                              int sample_period);
+long tnet_feacat_add_reader(TnetFeaCat* f, TnetFeatureReader* r, long max_utts);
+int tnet_feacat_finish(TnetFeaCat* f);
+int tnet_feacat_fetch(TnetFeaCat* f, int index, float* out, long cap, int* rows, int* cols, int* sample_period,
+                      char* logical, int logical_cap);
+int tnet_feacat_stats(TnetFeaCat* f, long* frames, long* utterances, long* packs, int* packed);
+int tnet_feacat_free(TnetFeaCat* f);
+int tnet_htk_write(const char* path, const float* data, int rows, int cols, int sample_period, int kind, int swap);
+
 /* ---- RBM pre-training (CuRbm, cuRbm.cc; the TRbmCu loop, TRbmCu.cc:291-357) ----------------
  * <rbm> parameters: W [n_vis x n_hid] (host row-major), visible / hidden biases; types[0..1] =
  * visible / hidden unit type (0 Bernoulli, 1 Gaussian; -1 in set = keep). */

@@ -9,6 +9,7 @@
 #include "curbm.h"
 #include "curecurrent.h"
 #include "cudiscrete.h"
+#include "cufeacat.h"
 #include "cunorm.h"
 #include "cushared.h"
 #include "cusparse.h"
@@ -59,6 +60,9 @@ struct TnetFeatureReader {
 };
 struct TnetNorm {
   std::unique_ptr<CuNormAccumulator> a;
+};
+struct TnetFeaCat {
+  std::unique_ptr<CuFeaCat> f;
 };
 struct TnetComm {
   std::unique_ptr<GradExchange> ex;
@@ -622,6 +626,88 @@ int tnet_norm_report(TnetNorm* n, char* buf, int cap) {
 }
 int tnet_norm_free(TnetNorm* n) {
   TRY_BEGIN delete n;
+  TRY_END
+}
+
+// ------------------------------------------------------------------------- forward pass
+TnetFeaCat* tnet_feacat_create(TnetNetwork* net, TnetNetwork* transform, int start_ext, int end_ext, int mode,
+                               int pack_rows) {
+  try {
+    if (!net) Error("tnet_feacat_create: null network");
+    if (start_ext < 0 || end_ext < 0) Error("tnet_feacat_create: negative frame extension");
+    if (pack_rows < -1) Error("tnet_feacat_create: pack_rows below -1");
+    std::unique_ptr<TnetFeaCat> h(new TnetFeaCat);
+    h->f.reset(new CuFeaCat(&net->net, transform ? &transform->net : nullptr, (size_t)start_ext, (size_t)end_ext, mode,
+                            (size_t)(pack_rows > 0 ? pack_rows : 0), pack_rows != -1));
+    return h.release();
+  }
+  TRY_END_PTR
+}
+int tnet_feacat_set_output(TnetFeaCat* f, const char* dir, const char* ext, int swap) {
+  TRY_BEGIN if (!f) Error("tnet_feacat_set_output: null handle");
+  if (!dir && !ext) f->f->SetSwap(swap != 0);
+  else f->f->SetOutput(dir, ext, swap != 0);
+  TRY_END
+}
+int tnet_feacat_add_utterance(TnetFeaCat* f, const float* feats, int rows, int cols, int ld, const char* logical_name,
+                              int sample_period) {
+  TRY_BEGIN if (!f) Error("tnet_feacat_add_utterance: null handle");
+  if (rows < 0 || cols < 0 || ld < 0) Error("tnet_feacat_add_utterance: negative dimension");
+  f->f->AddUtterance(feats, (size_t)rows, (size_t)cols, (size_t)ld, logical_name ? logical_name : "", sample_period);
+  TRY_END
+}
+long tnet_feacat_add_reader(TnetFeaCat* f, TnetFeatureReader* r, long max_utts) {
+  try {
+    if (!f || !r) Error("tnet_feacat_add_reader: null handle");
+    return f->f->AddReader(*r->r, (size_t)r->start_ext, (size_t)r->end_ext, max_utts);
+  } catch (std::exception& e) {
+    g_last_error = e.what();
+    return TNET_ERR_RUNTIME;
+  }
+}
+int tnet_feacat_finish(TnetFeaCat* f) {
+  TRY_BEGIN if (!f) Error("tnet_feacat_finish: null handle");
+  f->f->Finish();
+  TRY_END
+}
+int tnet_feacat_fetch(TnetFeaCat* f, int index, float* out, long cap, int* rows, int* cols, int* sample_period,
+                      char* logical, int logical_cap) {
+  try {
+    if (!f) Error("tnet_feacat_fetch: null handle");
+    if (index < 0 || (size_t)index >= f->f->Results()) return 0;
+    const CuFeaCat::Result& r = f->f->Fetch((size_t)index);
+    if (rows) *rows = (int)r.rows;
+    if (cols) *cols = (int)r.cols;
+    if (sample_period) *sample_period = r.sample_period;
+    if (logical && logical_cap > 0) {
+      std::strncpy(logical, r.logical.c_str(), (size_t)logical_cap - 1);
+      logical[logical_cap - 1] = 0;
+    }
+    if (out) {
+      if (cap < (long)(r.rows * r.cols)) Error("tnet_feacat_fetch: output buffer too small");
+      std::memcpy(out, r.words.get(), r.rows * r.cols * sizeof(uint32_t));
+    }
+    return 1;
+  } catch (std::exception& e) {
+    g_last_error = e.what();
+    return TNET_ERR_RUNTIME;
+  }
+}
+int tnet_feacat_stats(TnetFeaCat* f, long* frames, long* utterances, long* packs, int* packed) {
+  TRY_BEGIN if (!f) Error("tnet_feacat_stats: null handle");
+  if (frames) *frames = (long)f->f->Frames();
+  if (utterances) *utterances = (long)f->f->Utterances();
+  if (packs) *packs = (long)f->f->Packs();
+  if (packed) *packed = f->f->Packed() ? 1 : 0;
+  TRY_END
+}
+int tnet_feacat_free(TnetFeaCat* f) {
+  TRY_BEGIN delete f;
+  TRY_END
+}
+int tnet_htk_write(const char* path, const float* data, int rows, int cols, int sample_period, int kind, int swap) {
+  TRY_BEGIN if (!path || rows < 0 || cols <= 0 || (rows && !data)) Error("tnet_htk_write: bad arguments");
+  tnetio::WriteHtk(path, data, (size_t)rows, (size_t)cols, sample_period, kind, swap != 0, swap != 0);
   TRY_END
 }
 

@@ -62,6 +62,10 @@ class CuComponent {
   virtual ComponentType GetType() const = 0;
   virtual const char* GetName() const = 0;
   virtual bool IsUpdatable() const { return false; }
+  /// Row i of the output depends on row i of the input alone (no <expand> splice, no recurrence): rows of several
+  /// utterances may then share one Propagate (the forward pass packs them, cufeacat.h).  False unless a component
+  /// says otherwise.
+  virtual bool IsRowWise() const { return false; }
 
   size_t GetNInputs() const { return mNInputs; }
   size_t GetNOutputs() const { return mNOutputs; }

@@ -24,6 +24,7 @@ class CuDiscreteLinearity : public CuUpdatableComponent {
   CuDiscreteLinearity& operator=(const CuDiscreteLinearity&) = delete;
 
   ComponentType GetType() const override { return DISCRETE_LINEARITY; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<discretelinearity>"; }
 
   void PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) override;

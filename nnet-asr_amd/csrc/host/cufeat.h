@@ -42,6 +42,7 @@ class CuCopy : public CuComponent {
  public:
   CuCopy(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
   ComponentType GetType() const override { return COPY; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<copy>"; }
   void ReadFromStream(std::istream& rIn) override;
   void WriteToStream(std::ostream& rOut) override;
@@ -59,6 +60,7 @@ class CuTranspose : public CuComponent {
   CuTranspose(size_t nInputs, size_t nOutputs, CuComponent* pPred)
       : CuComponent(nInputs, nOutputs, pPred), mContext(0) {}
   ComponentType GetType() const override { return TRANSPOSE; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<transpose>"; }
   void ReadFromStream(std::istream& rIn) override;
   void WriteToStream(std::ostream& rOut) override;
@@ -75,6 +77,7 @@ class CuBlockLinearity : public CuComponent {
  public:
   CuBlockLinearity(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
   ComponentType GetType() const override { return BLOCK_LINEARITY; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<blocklinearity>"; }
   void ReadFromStream(std::istream& rIn) override;
   void WriteToStream(std::ostream& rOut) override;
@@ -90,6 +93,7 @@ class CuBias : public CuComponent {
  public:
   CuBias(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
   ComponentType GetType() const override { return BIAS; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<bias>"; }
   void ReadFromStream(std::istream& rIn) override;
   void WriteToStream(std::ostream& rOut) override;
@@ -105,6 +109,7 @@ class CuWindow : public CuComponent {
  public:
   CuWindow(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
   ComponentType GetType() const override { return WINDOW; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<window>"; }
   void ReadFromStream(std::istream& rIn) override;
   void WriteToStream(std::ostream& rOut) override;
@@ -120,6 +125,7 @@ class CuLog : public CuComponent {
  public:
   CuLog(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
   ComponentType GetType() const override { return LOG; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<log>"; }
 
  protected:

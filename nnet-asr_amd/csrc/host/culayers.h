@@ -21,6 +21,7 @@ class CuBiasedLinearity : public CuUpdatableComponent {
   }
 
   ComponentType GetType() const override { return BIASED_LINEARITY; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<biasedlinearity>"; }
 
   void PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) override;
@@ -121,6 +122,7 @@ class CuSigmoid : public CuComponent {
  public:
   CuSigmoid(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
   ComponentType GetType() const override { return SIGMOID; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<sigmoid>"; }
 
  protected:
@@ -132,6 +134,7 @@ class CuSoftmax : public CuComponent {
  public:
   CuSoftmax(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
   ComponentType GetType() const override { return SOFTMAX; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<softmax>"; }
 
  protected:
@@ -146,6 +149,7 @@ class CuBlockSoftmax : public CuComponent {
  public:
   CuBlockSoftmax(size_t nInputs, size_t nOutputs, CuComponent* pPred) : CuComponent(nInputs, nOutputs, pPred) {}
   ComponentType GetType() const override { return BLOCK_SOFTMAX; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<blocksoftmax>"; }
 
   void ReadFromStream(std::istream& rIn) override;

@@ -24,6 +24,7 @@ class CuSharedLinearity : public CuUpdatableComponent {
       : CuUpdatableComponent(nInputs, nOutputs, pPred), mNInstances(0) {}
 
   ComponentType GetType() const override { return SHARED_LINEARITY; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<sharedlinearity>"; }
 
   void PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) override;

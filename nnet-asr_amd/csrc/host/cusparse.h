@@ -19,6 +19,7 @@ class CuSparseLinearity : public CuUpdatableComponent {
       : CuUpdatableComponent(nInputs, nOutputs, pPred) {}
 
   ComponentType GetType() const override { return SPARSE_LINEARITY; }
+  bool IsRowWise() const override { return true; }
   const char* GetName() const override { return "<sparselinearity>"; }
 
   void PropagateFnc(const CuMatrix<BaseFloat>& X, CuMatrix<BaseFloat>& Y) override;

@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <cctype>
+#include <cerrno>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -390,6 +391,55 @@ std::string MakeHtkFileName(const std::string& in, const char* outDir, const cha
   }
   if (outExt && *outExt) o += std::string(".") + outExt;
   return o;
+}
+
+void EncodeHtkHeader(unsigned char* head, size_t rows, size_t cols, int samplePeriod, int kind, bool swap) {
+  uint32_t n = (uint32_t)rows, per = (uint32_t)samplePeriod;
+  uint16_t size = (uint16_t)(4 * cols), k = (uint16_t)kind;
+  if (swap) {
+    n = bswap32(n);
+    per = bswap32(per);
+    size = bswap16(size);
+    k = bswap16(k);
+  }
+  memcpy(head, &n, 4);
+  memcpy(head + 4, &per, 4);
+  memcpy(head + 8, &size, 2);
+  memcpy(head + 10, &k, 2);
+}
+
+void WriteHtk(const std::string& path, const void* words, size_t rows, size_t cols, int samplePeriod, int kind,
+              bool swap_header, bool swap_body) {
+  if (cols > 8191) {
+    std::ostringstream os;
+    os << "Cannot write " << path << ": " << cols << " columns do not fit the 16-bit sample size of an HTK header";
+    Fail(os.str());
+  }
+  if (rows > 0x7fffffffu) Fail("Cannot write " + path + ": too many rows");
+  FILE* fp = fopen(path.c_str(), "wb");
+  if (!fp) Fail("Cannot open output feature file: '" + path + "': " + strerror(errno));
+  unsigned char head[12];
+  EncodeHtkHeader(head, rows, cols, samplePeriod, kind, swap_header);
+  bool ok = fwrite(head, 1, 12, fp) == 12;
+  const size_t total = rows * cols;
+  const uint32_t* w = (const uint32_t*)words;
+  if (ok && total) {
+    if (!swap_body) {
+      ok = fwrite(w, 4, total, fp) == total;
+    } else {
+      std::vector<uint32_t> buf(std::min<size_t>(total, 1 << 16));
+      for (size_t done = 0; ok && done < total; done += buf.size()) {
+        const size_t m = std::min(buf.size(), total - done);
+        for (size_t i = 0; i < m; i++) buf[i] = bswap32(w[done + i]);
+        ok = fwrite(buf.data(), 4, m, fp) == m;
+      }
+    }
+  }
+  if (fclose(fp) != 0) ok = false;
+  if (!ok) {
+    remove(path.c_str());
+    Fail("Cannot write to output feature file: '" + path + "'");
+  }
 }
 
 // ------------------------------------------------------------------------------------------- MLF

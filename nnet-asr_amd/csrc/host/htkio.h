@@ -105,6 +105,16 @@ HtkHeader ReadHtkHeader(const std::string& physical, bool swap, const std::strin
 // MakeHtkFileName (Common.cc:118-172)
 std::string MakeHtkFileName(const std::string& in, const char* outDir, const char* outExt);
 
+// WriteHTKFeatures (Features.cc:1621-1673) for an uncompressed kind: the 12-byte header (nSamples = rows, the sample
+// period, sampleSize = 4 * cols, the kind) and rows * cols 32-bit words.  swap_header / swap_body: store byte-reversed
+// (the forward pass hands over a body the device has already reversed: header only).  cols > 8191 does not fit the
+// int16 sampleSize (the reference overflows silently): an error.  Throws naming the file; a file that could not be
+// written in full is removed.
+enum : int { kParmUser = 9 };
+void EncodeHtkHeader(unsigned char* head12, size_t rows, size_t cols, int samplePeriod, int kind, bool swap);
+void WriteHtk(const std::string& path, const void* words, size_t rows, size_t cols, int samplePeriod, int kind,
+              bool swap_header, bool swap_body);
+
 // LabelRepository: the MLF indexed once (pattern -> its segment lines), the state-tag map
 // (ReadOutputLabelMap, Labels.cc:192-212).  Lookups are const and thread-safe.
 class MlfLabels {

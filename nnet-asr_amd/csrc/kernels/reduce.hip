@@ -10,6 +10,7 @@
 
 #include "kcommon.h"
 #include "rbm_stats.h"
+#include "softmax_row.h"
 
 namespace tnetk {
 
@@ -91,9 +92,6 @@ static int colsum_run(const float* M, TnetMatrixDim d, void* workspace, hipStrea
 // ---------------------------------------------------------------------------------------------
 // softmax / cross-entropy, one wave per row
 // ---------------------------------------------------------------------------------------------
-constexpr int SX_MAXV4 = 16;  // row held in registers up to 16 float4 per lane = 4096 columns
-
-
 
 // KIND 0: class-id labels; KIND 1: dense targets D.  Z == nullptr: Y already holds softmax output.
 template <int KIND>
@@ -119,48 +117,10 @@ __global__ __launch_bounds__(256) void softmax_xent_kernel(const float* __restri
   int t = (KIND == 0) ? labels[row] : -1;
   if (t >= N) t = -1;
 
-  // ---- pass 1: max
+  // ---- passes 1 and 2: the row maximum and 1 / sum of exp (softmax_row.h, shared with the forward pass's emit)
   f32x4 rv[SX_MAXV4];
-  float m = -1e20f;
-  if (cached) {
-#pragma unroll
-    for (int j = 0; j < SX_MAXV4; ++j) {
-      const int c = j * 256 + lane * 4;
-      f32x4 x = {-1e30f, -1e30f, -1e30f, -1e30f};
-      if (c < N) x = *reinterpret_cast<const f32x4*>(src + c);
-      rv[j] = x;
-      m = fmaxf(m, fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
-    }
-  } else {
-    for (int c = lane; c < N; c += 64) m = fmaxf(m, src[c]);
-  }
-  m = wave_max(m);
-
-  // ---- pass 2: sum of exp (only when normalising logits)
-  float inv = 1.f;
-  double dsum = 0.0;
-  if (Z) {
-    float s = 0.f;
-    if (cached) {
-#pragma unroll
-      for (int j = 0; j < SX_MAXV4; ++j) {
-        const int c = j * 256 + lane * 4;
-        if (c < N) {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            const float e = fast_exp(rv[j][k] - m);
-            rv[j][k] = e;
-            s += e;
-          }
-        }
-      }
-    } else {
-      for (int c = lane; c < N; c += 64) s += fast_exp(src[c] - m);
-    }
-    dsum = wave_sum_d((double)s);
-  }
-  const float sum = (float)dsum;
-  const float rsum = 1.f / sum;  // one division per row; y = e * (1/sum)
+  float m, rsum;
+  softmax_row_norm(src, N, lane, cached, Z != nullptr, rv, m, rsum);
 
   // ---- pass 3: y, error, argmax, xent
   ArgMax ay{-1e20f, 0x7fffffff}, ad{-1e20f, 0x7fffffff};

@@ -16,8 +16,8 @@ from . import formats  # noqa: F401  (host formats; no device code)
 from ._lib import HOST_ALLREDUCE_FN, LIB_PATH, MatrixDim, TnetError, check, check_ptr, header_symbols, lib
 
 __all__ = ["DeviceArray", "Network", "Objective", "Trainer", "RbmTrainer", "RnnTrainer", "Comm", "TnetError", "synchronize",
-           "Normalizer",
-           "FeatureReader", "htk_read", "mask_match", "mlf_lookup",
+           "Normalizer", "Forwarder",
+           "FeatureReader", "htk_read", "htk_write", "mask_match", "mlf_lookup",
            "pad_stride",
            "device_count", "version", "LIB_PATH", "header_symbols", "formats"]
 
@@ -676,6 +676,97 @@ class Normalizer:
                 self.h = None
         except Exception:
             pass
+
+
+class Forwarder:
+    """The TFeaCatCu pass (src/TFeaCatCu.cc:215-270): a trained network turned into posterior / bottleneck features.
+
+    Utterances carry start_ext / end_ext context rows for the transform's <expand>; the rows between them are packed
+    back to back into bunches of pack_rows rows (None: the library's default; -1: never pack), the network runs once per
+    pack, and one
+    emit kernel applies gmm_bypass (sqrt(-2 log y)) then log_posterior (log y), the byte order and the dense file
+    layout on the device.  A network with a component that mixes rows is run one utterance a pass instead
+    (stats()["packed"] is False).  An empty network copies the transform's output.
+
+    Without set_output the results are kept: results() yields (logical name, float32 [rows x n_out], sample period)
+    in the order added.  With set_output(dir, ext) every utterance becomes the HTK file dir/basename(logical).ext
+    (kind USER, big-endian unless swap=False), written by a small writer pool."""
+
+    GMMBYPASS, LOGPOSTERIOR = 1, 2
+
+    def __init__(self, net: Network, transform: Optional[Network] = None, start_ext: int = 0, end_ext: int = 0,
+                 log_posterior: bool = False, gmm_bypass: bool = False, pack_rows: Optional[int] = None):
+        self._net, self._transform = net, transform   # borrowed by the C++ object: keep them alive
+        self.start_ext, self.end_ext = int(start_ext), int(end_ext)
+        self.mode = (self.GMMBYPASS if gmm_bypass else 0) | (self.LOGPOSTERIOR if log_posterior else 0)
+        self._files = False
+        self.h = check_ptr(lib().tnet_feacat_create(net.h, transform.h if transform is not None else None,
+                                                    self.start_ext, self.end_ext, self.mode, int(pack_rows or 0)),
+                           "tnet_feacat_create")
+
+    def set_output(self, dir: Optional[str], ext: Optional[str] = "fea", swap: bool = True) -> None:
+        """file sink (before the first utterance); dir None: next to the logical names, as the reference"""
+        enc = lambda s: s.encode() if s is not None else None  # noqa: E731
+        check(lib().tnet_feacat_set_output(self.h, enc(dir), enc(ext if ext is not None else ""), int(swap)),
+              "feacat set_output")
+        self._files = True
+
+    def add(self, feats: np.ndarray, name: str = "", sample_period: int = 100000) -> None:
+        """one utterance [rows incl. the context rows x dim]"""
+        feats, _ = _utterance(feats, None, "Forwarder.add")
+        check(lib().tnet_feacat_add_utterance(self.h, feats.ctypes.data, feats.shape[0], feats.shape[1],
+                                              feats.shape[1], name.encode(), int(sample_period)), "feacat add")
+
+    def add_reader(self, reader: "FeatureReader", max_utts: int = -1) -> int:
+        """the TFeaCatCu main loop over a native FeatureReader (same start_ext / end_ext); returns the frames emitted"""
+        n = lib().tnet_feacat_add_reader(self.h, reader.h, max_utts)
+        if n < 0:
+            check(int(n), "feacat add_reader")
+        return int(n)
+
+    def finish(self) -> None:
+        check(lib().tnet_feacat_finish(self.h), "feacat finish")
+
+    def stats(self) -> dict:
+        fr, ut, pk, pd = C.c_long(), C.c_long(), C.c_long(), C.c_int()
+        check(lib().tnet_feacat_stats(self.h, C.byref(fr), C.byref(ut), C.byref(pk), C.byref(pd)), "feacat stats")
+        return dict(frames=int(fr.value), utterances=int(ut.value), packs=int(pk.value), packed=bool(pd.value))
+
+    def results(self):
+        """memory sink, after finish(): [(logical name, float32 [rows x n_out], sample period)]"""
+        if self._files:
+            raise TnetError("Forwarder.results: the results went to files")
+        out = []
+        for i in range(self.stats()["utterances"]):
+            rows, cols, per = C.c_int(), C.c_int(), C.c_int()
+            name = C.create_string_buffer(4096)
+            st = lib().tnet_feacat_fetch(self.h, i, None, 0, C.byref(rows), C.byref(cols), C.byref(per), name, len(name))
+            check(min(st, 0), "feacat fetch")
+            if st == 0:
+                break
+            y = np.empty((rows.value, cols.value), np.float32)
+            check(min(lib().tnet_feacat_fetch(self.h, i, y.ctypes.data, y.size, None, None, None, None, 0), 0),
+                  "feacat fetch")
+            out.append((name.value.decode(), y, per.value))
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None):
+                lib().tnet_feacat_free(self.h)
+                self.h = None
+        except Exception:
+            pass
+
+
+def htk_write(path: str, data: np.ndarray, sample_period: int = 100000, kind: int = 9, swap: bool = True) -> None:
+    """one uncompressed HTK file through the native writer (host only): header + rows x cols floats, big-endian
+    unless swap=False; kind 9 = USER"""
+    data = np.ascontiguousarray(data, np.float32)
+    if data.ndim != 2:
+        raise ValueError(f"htk_write: data must be 2-D, got shape {data.shape}")
+    check(lib().tnet_htk_write(path.encode(), data.ctypes.data, data.shape[0], data.shape[1], int(sample_period),
+                               int(kind), int(swap)), "htk_write")
 
 
 def shard_utterances(items: Sequence, rank: int, world: int) -> list:

@@ -222,6 +222,17 @@ _SIGS = {
     "tnet_norm_write": (i32, [vp, C.c_char_p]),
     "tnet_norm_report": (i32, [vp, C.c_char_p, i32]),
     "tnet_norm_free": (i32, [vp]),
+    "tnet_feacat_emit": (i32, [vp, MatrixDim, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "tnet_softmax_emit": (i32, [vp, MatrixDim, vp, vp, vp, i32, i32, i32, vp, vp]),
+    "tnet_feacat_create": (vp, [vp, vp, i32, i32, i32, i32]),
+    "tnet_feacat_set_output": (i32, [vp, C.c_char_p, C.c_char_p, i32]),
+    "tnet_feacat_add_utterance": (i32, [vp, vp, i32, i32, i32, C.c_char_p, i32]),
+    "tnet_feacat_add_reader": (i64, [vp, vp, i64]),
+    "tnet_feacat_finish": (i32, [vp]),
+    "tnet_feacat_fetch": (i32, [vp, i32, vp, i64, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.c_char_p, i32]),
+    "tnet_feacat_stats": (i32, [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i32)]),
+    "tnet_feacat_free": (i32, [vp]),
+    "tnet_htk_write": (i32, [C.c_char_p, vp, i32, i32, i32, i32, i32]),
     "tnet_comm_unique_id": (i32, [C.c_char_p]),
     "tnet_comm_create": (vp, [i32, i32, C.c_char_p]),
     "tnet_comm_free": (i32, [vp]),
