@@ -514,7 +514,10 @@ void CuNetwork::TrainBunch(const CuMatrix<BaseFloat>& X, const CuVector<int>& la
     CuMatrix<BaseFloat>& cp = *mColPart[nl - 1];
     KTScope kt("colsum:" + std::to_string(GetNOutputs()), 4.0 * rows * GetNOutputs());
     const int st = tnet_colsum_slab_sums(mGlobErr.pCUData(), mGlobErr.Dim(), cp.pCUData(), (int)cp.Stride(), S);
-    if (st == TNET_ERR_UNSUPPORTED) return false;
+    if (st == TNET_ERR_UNSUPPORTED) {
+      kt.Cancel();  // nothing was launched: no `colsum` entry in the kernel-timing report
+      return false;
+    }
     TNET_SAFE_CALL(st);
     return true;
   };

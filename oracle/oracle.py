@@ -59,6 +59,26 @@ def lib():
     return _LIB
 
 
+_LIB64 = None
+
+
+def lib64():
+    """liboracle64.so: tnet_oracle.c with double storage (-DORC_DOUBLE); only the MLP step and forward"""
+    global _LIB64
+    if _LIB64 is None:
+        path = os.path.join(_HERE, "liboracle64.so")
+        if not os.path.exists(path):
+            raise RuntimeError(f"{path} missing: run `make -C oracle`")
+        L = C.CDLL(path)
+        f64p = np.ctypeslib.ndpointer(np.float64, flags="C_CONTIGUOUS")
+        L.orc_mlp_step.argtypes = [C.c_int, i32p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f64p, i32p,
+                                   C.c_int, C.c_double, C.c_double, C.c_double, C.c_int, C.c_int, f64p, f64p,
+                                   C.POINTER(C.c_double), C.POINTER(C.c_long)]
+        L.orc_mlp_forward.argtypes = [C.c_int, i32p, C.c_void_p, C.c_void_p, f64p, C.c_int, f64p]
+        _LIB64 = L
+    return _LIB64
+
+
 def _ptrs(arrs):
     return (C.c_void_p * len(arrs))(*[a.ctypes.data for a in arrs])
 
@@ -126,11 +146,16 @@ def epoch_schedule(lens, cachesize, bunch, seed, randomize=True):
 
 
 class MLP:
-    """Oracle MLP state: weights W[l] [n_in x n_out], biases, momentum buffers."""
+    """Oracle MLP state: weights W[l] [n_in x n_out], biases, momentum buffers.  dtype float64: the same C program
+    built with double storage (liboracle64.so), for pinning a float64 restatement to it."""
 
-    def __init__(self, Ws, bs):
-        self.W = [np.ascontiguousarray(w, np.float32).copy() for w in Ws]
-        self.b = [np.ascontiguousarray(x, np.float32).copy() for x in bs]
+    def __init__(self, Ws, bs, dtype=np.float32):
+        self.dt = np.dtype(dtype).type
+        if self.dt not in (np.float32, np.float64):
+            raise ValueError("oracle.MLP: float32 or float64")
+        self._lib = lib if self.dt is np.float32 else lib64
+        self.W = [np.ascontiguousarray(w, self.dt).copy() for w in Ws]
+        self.b = [np.ascontiguousarray(x, self.dt).copy() for x in bs]
         self.cW = [np.zeros_like(w) for w in self.W]
         self.cb = [np.zeros_like(x) for x in self.b]
         self.dims = np.array([self.W[0].shape[0]] + [w.shape[1] for w in self.W], np.int32)
@@ -139,19 +164,19 @@ class MLP:
         self.frames = 0
 
     @classmethod
-    def from_layers(cls, layers):
+    def from_layers(cls, layers, dtype=np.float32):
         lin = [L for L in layers if L.tag == "<biasedlinearity>"]
-        return cls([L.W for L in lin], [L.b for L in lin])
+        return cls([L.W for L in lin], [L.b for L in lin], dtype)
 
     def step(self, X, labels, lr, mmt=0.0, wc=0.0, graddivfrm=True, cpu_semantics=False):
-        X = np.ascontiguousarray(X, np.float32)
+        X = np.ascontiguousarray(X, self.dt)
         labels = np.ascontiguousarray(labels, np.int32)
         B = X.shape[0]
-        Y = np.empty((B, self.dims[-1]), np.float32)
+        Y = np.empty((B, self.dims[-1]), self.dt)
         E = np.empty_like(Y)
         xe = C.c_double(0.0)
         cor = C.c_long(0)
-        lib().orc_mlp_step(len(self.W), self.dims, _ptrs(self.W), _ptrs(self.b), _ptrs(self.cW), _ptrs(self.cb),
+        self._lib().orc_mlp_step(len(self.W), self.dims, _ptrs(self.W), _ptrs(self.b), _ptrs(self.cW), _ptrs(self.cb),
                            X, labels, B, lr, mmt, wc, int(graddivfrm), int(cpu_semantics), Y, E,
                            C.byref(xe), C.byref(cor))
         self.xent += xe.value
@@ -160,9 +185,9 @@ class MLP:
         return Y, E
 
     def forward(self, X):
-        X = np.ascontiguousarray(X, np.float32)
-        Y = np.empty((X.shape[0], self.dims[-1]), np.float32)
-        lib().orc_mlp_forward(len(self.W), self.dims, _ptrs(self.W), _ptrs(self.b), X, X.shape[0], Y)
+        X = np.ascontiguousarray(X, self.dt)
+        Y = np.empty((X.shape[0], self.dims[-1]), self.dt)
+        self._lib().orc_mlp_forward(len(self.W), self.dims, _ptrs(self.W), _ptrs(self.b), X, X.shape[0], Y)
         return Y
 
 

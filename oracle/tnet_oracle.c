@@ -22,6 +22,17 @@
 #include <stdlib.h>
 #include <string.h>
 
+/* orc_real: the storage type of the MLP path (orc_sgemm ... orc_mlp_forward below).  float in liboracle.so; double
+ * in liboracle64.so (make: -DORC_DOUBLE), where storage then rounds nothing: oracle.MLP with dtype float64 calls
+ * orc_mlp_step / orc_mlp_forward there to show that a float64 restatement of the step is THIS algorithm (agreement to
+ * 1e-12), which float32 storage can show to 1e-7 only.  What lies behind the MLP path (random generators, RBM, RNN,
+ * front end) is compiled into the float build only. */
+#ifdef ORC_DOUBLE
+typedef double orc_real;
+#else
+typedef float orc_real;
+#endif
+
 /* ---------------------------------------------------------------------------------------
  * drand48 family (glibc published algorithm): X_{n+1} = (a X_n + c) mod 2^48,
  * a = 0x5DEECE66D, c = 0xB; srand48(s): X = (s << 16) | 0x330E; lrand48 = X >> 17.
@@ -112,21 +123,21 @@ long orc_epoch_schedule_x(const int* lens, int nutt, int cachesize, int bunch, u
  * Reference: CuMatrix::Gemm (src/CuBaseLib/cumatrix.tcc:336-370), Matrix::BlasGemm
  * (src/KaldiLib/Matrix.cc:161-199).
  * ------------------------------------------------------------------------------------- */
-void orc_sgemm(char ta, char tb, int M, int N, int K, float alpha, const float* A, int lda,
-               const float* B, int ldb, float beta, float* C, int ldc) {
+void orc_sgemm(char ta, char tb, int M, int N, int K, orc_real alpha, const orc_real* A, int lda,
+               const orc_real* B, int ldb, orc_real beta, orc_real* C, int ldc) {
   int tA = (ta == 'T' || ta == 't'), tB = (tb == 'T' || tb == 't');
   /* pack op(A) as [M x K] and op(B)^T as [N x K] (both K-contiguous), then double dots */
-  float* Ap = (float*)malloc(sizeof(float) * (size_t)M * K);
-  float* Bp = (float*)malloc(sizeof(float) * (size_t)N * K);
+  orc_real* Ap = (orc_real*)malloc(sizeof(orc_real) * (size_t)M * K);
+  orc_real* Bp = (orc_real*)malloc(sizeof(orc_real) * (size_t)N * K);
   for (int i = 0; i < M; i++)
     for (int k = 0; k < K; k++) Ap[(size_t)i * K + k] = tA ? A[(size_t)k * lda + i] : A[(size_t)i * lda + k];
   for (int j = 0; j < N; j++)
     for (int k = 0; k < K; k++) Bp[(size_t)j * K + k] = tB ? B[(size_t)j * ldb + k] : B[(size_t)k * ldb + j];
 #pragma omp parallel for schedule(dynamic, 4)
   for (int i = 0; i < M; i++) {
-    const float* a = Ap + (size_t)i * K;
+    const orc_real* a = Ap + (size_t)i * K;
     for (int j = 0; j < N; j++) {
-      const float* bb = Bp + (size_t)j * K;
+      const orc_real* bb = Bp + (size_t)j * K;
       double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
       int k = 0;
       for (; k + 4 <= K; k += 4) {
@@ -137,48 +148,48 @@ void orc_sgemm(char ta, char tb, int M, int N, int K, float alpha, const float* 
       }
       for (; k < K; k++) s0 += (double)a[k] * bb[k];
       double acc = (s0 + s1) + (s2 + s3);
-      float* c = C + (size_t)i * ldc + j;
-      *c = (float)(alpha * acc + (beta == 0.0f ? 0.0 : (double)beta * *c));
+      orc_real* c = C + (size_t)i * ldc + j;
+      *c = (orc_real)(alpha * acc + (beta == 0.0f ? 0.0 : (double)beta * *c));
     }
   }
   free(Ap); free(Bp);
 }
 
 /* y = b + X W  (CuBiasedLinearity::PropagateFnc, cuBiasedLinearity.cc:11-16) */
-void orc_affine(const float* X, int rows, int n_in, const float* W, const float* b, int n_out, float* Y) {
+void orc_affine(const orc_real* X, int rows, int n_in, const orc_real* W, const orc_real* b, int n_out, orc_real* Y) {
   orc_sgemm('N', 'N', rows, n_out, n_in, 1.0f, X, n_in, W, n_out, 0.0f, Y, n_out);
   for (int r = 0; r < rows; r++)
     for (int c = 0; c < n_out; c++) Y[(size_t)r * n_out + c] += b[c];
 }
 
 /* _sigmoid (cukernels.cu:192-206): 1.0/(1.0+exp(-x)) with double constants */
-void orc_sigmoid(float* y, const float* x, long n) {
-  for (long i = 0; i < n; i++) y[i] = (float)(1.0 / (1.0 + exp(-(double)x[i])));
+void orc_sigmoid(orc_real* y, const orc_real* x, long n) {
+  for (long i = 0; i < n; i++) y[i] = (orc_real)(1.0 / (1.0 + exp(-(double)x[i])));
 }
 
 /* _diff_sigmoid (cukernels.cu:209-217): e_out = y (1 - y) e */
-void orc_diff_sigmoid(float* eout, const float* e, const float* y, long n) {
-  for (long i = 0; i < n; i++) eout[i] = (float)((double)y[i] * (1.0 - (double)y[i]) * (double)e[i]);
+void orc_diff_sigmoid(orc_real* eout, const orc_real* e, const orc_real* y, long n) {
+  for (long i = 0; i < n; i++) eout[i] = (orc_real)((double)y[i] * (1.0 - (double)y[i]) * (double)e[i]);
 }
 
 /* _softmax (cukernels.cu:220-242): double max / sum, y = exp(x - max) / sum */
-void orc_softmax(float* y, const float* x, int rows, int cols) {
+void orc_softmax(orc_real* y, const orc_real* x, int rows, int cols) {
   for (int r = 0; r < rows; r++) {
-    const float* xr = x + (size_t)r * cols;
-    float* yr = y + (size_t)r * cols;
+    const orc_real* xr = x + (size_t)r * cols;
+    orc_real* yr = y + (size_t)r * cols;
     double mx = -1e20, sum = 0.0;
     for (int c = 0; c < cols; c++) if (mx < xr[c]) mx = xr[c];
-    for (int c = 0; c < cols; c++) { double e = exp((double)xr[c] - mx); yr[c] = (float)e; sum += yr[c]; }
-    for (int c = 0; c < cols; c++) yr[c] = (float)((double)yr[c] / sum);
+    for (int c = 0; c < cols; c++) { double e = exp((double)xr[c] - mx); yr[c] = (orc_real)e; sum += yr[c]; }
+    for (int c = 0; c < cols; c++) yr[c] = (orc_real)((double)yr[c] / sum);
   }
 }
 
 /* v = alpha * sum_rows(M) + beta * v, double accumulation (_add_col_sum, cukernels.cu:147-164) */
-void orc_add_col_sum(float alpha, const float* M, int rows, int cols, float beta, float* v) {
+void orc_add_col_sum(orc_real alpha, const orc_real* M, int rows, int cols, orc_real beta, orc_real* v) {
   for (int c = 0; c < cols; c++) {
     double s = 0.0;
     for (int r = 0; r < rows; r++) s += M[(size_t)r * cols + c];
-    v[c] = (float)(alpha * s + (double)beta * v[c]);
+    v[c] = (orc_real)(alpha * s + (double)beta * v[c]);
   }
 }
 
@@ -188,17 +199,17 @@ void orc_add_col_sum(float alpha, const float* M, int rows, int cols, float beta
  *                                                   FindMaxId, src/TNetLib/ObjFun.cc:64-74)
  *   xent += -sum_c d log(max(y, FLT_MIN))          (cuObjectiveFunction.cc:72-80, _log_elem)
  */
-void orc_xent_eval(const float* y, const int* lab, int rows, int cols, float* err, double* xent,
+void orc_xent_eval(const orc_real* y, const int* lab, int rows, int cols, orc_real* err, double* xent,
                    long* correct) {
   for (int r = 0; r < rows; r++) {
-    const float* yr = y + (size_t)r * cols;
+    const orc_real* yr = y + (size_t)r * cols;
     int t = lab[r];
-    int am = -1; float mv = -1e20f;
+    int am = -1; orc_real mv = -1e20f;
     for (int c = 0; c < cols; c++) if (yr[c] > mv) { mv = yr[c]; am = c; }
     int des = t >= 0 ? t : 0;  /* all-zero target row: first max of zeros is column 0 */
     if (am == des) (*correct)++;
     if (t >= 0) {
-      float p = yr[t] < FLT_MIN ? FLT_MIN : yr[t];
+      orc_real p = yr[t] < FLT_MIN ? FLT_MIN : yr[t];
       *xent -= log((double)p);
     }
     if (err)
@@ -212,7 +223,7 @@ void orc_xent_eval(const float* y, const int* lab, int rows, int cols, float* er
  * layout of CuBiasedLinearity::mLinearity), updated in place.
  *
  * cpu_semantics=1: TNet --THREADS=1 (Platform.h:300-336; BiasedLinearity.cc:65-178):
- *     G = X^T E (float), g_b = sum_rows E (float loop); W += -lr * G; W += (-lr*wc*B) W;
+ *     G = X^T E (orc_real), g_b = sum_rows E (orc_real loop); W += -lr * G; W += (-lr*wc*B) W;
  *     b += -lr * g_b.
  * cpu_semantics=0: CuBiasedLinearity::Update "#if 1" branch (cuBiasedLinearity.cc:46-64):
  *     N = (gdf ? B : 1) / (1 - mmt); C_W = X^T E + mmt C_W; c_b = colsum(E) + mmt c_b;
@@ -221,54 +232,54 @@ void orc_xent_eval(const float* y, const int* lab, int rows, int cols, float* er
  * cW/cb (momentum buffers) are required only when cpu_semantics=0.
  * Outputs: Y (softmax output [B x nout]), E (top error [B x nout]), xent, correct (accumulated).
  * ------------------------------------------------------------------------------------- */
-int orc_mlp_step(int nl, const int* dims, float** W, float** b, float** cW, float** cb,
-                 const float* X, const int* lab, int B, float lr, float mmt, float wc, int gdf,
-                 int cpu_semantics, float* Y, float* E, double* xent, long* correct) {
-  float** act = (float**)calloc((size_t)nl + 1, sizeof(float*));   /* act[0] = X, act[l+1] = out of layer l */
-  act[0] = (float*)X;
+int orc_mlp_step(int nl, const int* dims, orc_real** W, orc_real** b, orc_real** cW, orc_real** cb,
+                 const orc_real* X, const int* lab, int B, orc_real lr, orc_real mmt, orc_real wc, int gdf,
+                 int cpu_semantics, orc_real* Y, orc_real* E, double* xent, long* correct) {
+  orc_real** act = (orc_real**)calloc((size_t)nl + 1, sizeof(orc_real*));   /* act[0] = X, act[l+1] = out of layer l */
+  act[0] = (orc_real*)X;
   for (int l = 0; l < nl; l++) {
     int n_in = dims[l], n_out = dims[l + 1];
-    float* z = (float*)malloc(sizeof(float) * (size_t)B * n_out);
+    orc_real* z = (orc_real*)malloc(sizeof(orc_real) * (size_t)B * n_out);
     orc_affine(act[l], B, n_in, W[l], b[l], n_out, z);
     if (l < nl - 1) orc_sigmoid(z, z, (long)B * n_out);
     else orc_softmax(z, z, B, n_out);
     act[l + 1] = z;
   }
   int nout = dims[nl];
-  memcpy(Y, act[nl], sizeof(float) * (size_t)B * nout);
-  float* e = (float*)malloc(sizeof(float) * (size_t)B * nout);
+  memcpy(Y, act[nl], sizeof(orc_real) * (size_t)B * nout);
+  orc_real* e = (orc_real*)malloc(sizeof(orc_real) * (size_t)B * nout);
   orc_xent_eval(act[nl], lab, B, nout, e, xent, correct);
-  memcpy(E, e, sizeof(float) * (size_t)B * nout);
+  memcpy(E, e, sizeof(orc_real) * (size_t)B * nout);
 
   for (int l = nl - 1; l >= 0; l--) {
     int n_in = dims[l], n_out = dims[l + 1];
-    float* e_in = NULL;
+    orc_real* e_in = NULL;
     if (l > 0) {  /* backprop with pre-update W, then through the sigmoid below */
-      e_in = (float*)malloc(sizeof(float) * (size_t)B * n_in);
+      e_in = (orc_real*)malloc(sizeof(orc_real) * (size_t)B * n_in);
       orc_sgemm('N', 'T', B, n_in, n_out, 1.0f, e, n_out, W[l], n_out, 0.0f, e_in, n_in);
       orc_diff_sigmoid(e_in, e_in, act[l], (long)B * n_in);
     }
     size_t nw = (size_t)n_in * n_out;
     if (cpu_semantics) {
-      float* G = (float*)malloc(sizeof(float) * nw);
+      orc_real* G = (orc_real*)malloc(sizeof(orc_real) * nw);
       orc_sgemm('T', 'N', n_in, n_out, B, 1.0f, act[l], n_in, e, n_out, 0.0f, G, n_out);
-      float* gb = (float*)calloc((size_t)n_out, sizeof(float));
+      orc_real* gb = (orc_real*)calloc((size_t)n_out, sizeof(orc_real));
       for (int r = 0; r < B; r++)
         for (int c = 0; c < n_out; c++) gb[c] += e[(size_t)r * n_out + c];
       for (size_t i = 0; i < nw; i++) W[l][i] = W[l][i] + (-lr) * G[i];
-      float l2 = -lr * wc * (float)B;
+      orc_real l2 = -lr * wc * (orc_real)B;
       if (l2 != 0.0f) for (size_t i = 0; i < nw; i++) W[l][i] = W[l][i] + l2 * W[l][i];
       for (int c = 0; c < n_out; c++) b[l][c] = b[l][c] + (-lr) * gb[c];
       free(G); free(gb);
     } else {
-      float N = gdf ? (float)B : 1.0f;
-      N *= (float)(1.0 / (1.0 - (double)mmt));
+      orc_real N = gdf ? (orc_real)B : 1.0f;
+      N *= (orc_real)(1.0 / (1.0 - (double)mmt));
       orc_sgemm('T', 'N', n_in, n_out, B, 1.0f, act[l], n_in, e, n_out, mmt, cW[l], n_out);
       orc_add_col_sum(1.0f, e, B, n_out, mmt, cb[l]);
-      float s = -lr / N;
+      orc_real s = -lr / N;
       for (size_t i = 0; i < nw; i++) W[l][i] = W[l][i] + s * cW[l][i];
       for (int c = 0; c < n_out; c++) b[l][c] = b[l][c] + s * cb[l][c];
-      float l2 = -lr * wc * (gdf ? 1.0f : (float)B);
+      orc_real l2 = -lr * wc * (gdf ? 1.0f : (orc_real)B);
       if (l2 != 0.0f) for (size_t i = 0; i < nw; i++) W[l][i] = W[l][i] + l2 * W[l][i];
     }
     free(e);
@@ -280,22 +291,26 @@ int orc_mlp_step(int nl, const int* dims, float** W, float** b, float** cW, floa
 }
 
 /* Forward only (TFeaCatCu / CuNetwork::Propagate): returns the network output Y. */
-int orc_mlp_forward(int nl, const int* dims, float** W, float** b, const float* X, int B, float* Y) {
-  const float* in = X;
-  float* buf = NULL;
+int orc_mlp_forward(int nl, const int* dims, orc_real** W, orc_real** b, const orc_real* X, int B, orc_real* Y) {
+  const orc_real* in = X;
+  orc_real* buf = NULL;
   for (int l = 0; l < nl; l++) {
     int n_in = dims[l], n_out = dims[l + 1];
-    float* z = (float*)malloc(sizeof(float) * (size_t)B * n_out);
+    orc_real* z = (orc_real*)malloc(sizeof(orc_real) * (size_t)B * n_out);
     orc_affine(in, B, n_in, W[l], b[l], n_out, z);
     if (l < nl - 1) orc_sigmoid(z, z, (long)B * n_out);
     else orc_softmax(z, z, B, n_out);
     free(buf);
     buf = z; in = z;
   }
-  memcpy(Y, buf, sizeof(float) * (size_t)B * dims[nl]);
+  memcpy(Y, buf, sizeof(orc_real) * (size_t)B * dims[nl]);
   free(buf);
   return 0;
 }
+
+/* Everything below calls the MLP path's helpers with float buffers: it exists in the float build only, so
+ * liboracle64.so exports no function whose arguments silently changed type. */
+#ifndef ORC_DOUBLE
 
 /* ---------------------------------------------------------------------------------------
  * Fast writer of a gen_mlp_init-style (--gauss --negbias) .nnet text file for the CPU baseline
@@ -530,3 +545,4 @@ int orc_rnn_utterance(int nIn, int H, int S, float* Wr, float* br, float* cbr, f
   free(hist); free(y); free(out); free(err); free(e); free(D);
   return 0;
 }
+#endif /* !ORC_DOUBLE */

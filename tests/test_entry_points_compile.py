@@ -10,7 +10,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.parametrize("name", ["bench.py", "__graft_entry__.py", "oracle/cpu_baseline.py",
                                   "tests/shadow_modes_worker.py", "tests/dp_worker.py",
-                                  "tests/rnn_modes_worker.py"])
+                                  "tests/rnn_modes_worker.py", "tests/step_modes_worker.py"])
 def test_entry_point_compiles(name, tmp_path):
     """bench.py's CPU leg (oracle/cpu_baseline.py) is imported only after the timed region on the GPU box"""
     path = os.path.join(REPO, name)

@@ -15,6 +15,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import oracle as orc  # noqa: E402
+import step_cases  # noqa: E402
 from golden_io import load_npz  # noqa: E402
 from tnet_amd import DeviceArray, Network, Objective, Trainer, formats  # noqa: E402
 
@@ -81,9 +82,11 @@ def test_train_bunch_gpu_semantics_vs_oracle(mmt, gdf, wc, lrf):
     refs = [orc.MLP([W[k]], [b[k]]) for k in range(3)]  # per-layer state holders
     ref = orc.MLP(W, b)
     B = 32
+    data = []
     for s in range(5):
         X = rng.standard_normal((B, dims[0])).astype(np.float32)
         L = rng.integers(0, dims[-1], B).astype(np.int32)
+        data.append((X, L))
         net.train_bunch(obj, DeviceArray.from_numpy(X), DeviceArray.vector(L))
         # oracle with per-layer learn rates: run one step per distinct factor set by scaling
         if lrf is None:
@@ -100,6 +103,20 @@ def test_train_bunch_gpu_semantics_vs_oracle(mmt, gdf, wc, lrf):
         Wg0, bg0 = net.linear_params()[0]
         np.testing.assert_array_equal(Wg0, W[0])
         np.testing.assert_array_equal(bg0, b[0])
+        # every layer -- the stopper at factor 1 and the top layer at factor 0.5 -- against the float64 restatement
+        # with per-layer rates (tests/step_cases.py; tests/test_step_cases_cpu.py shows that it tells a dropped factor
+        # and an updated frozen layer from the right step)
+        k = dict(lr=lr, mmt=mmt, wc=wc, l1=0.0, gdf=gdf)
+        steps, rst = step_cases.trajectory(layers, k, data, factors=lrf)
+        want = steps[-1][1]
+        for j, (Wg, bg) in enumerate(net.linear_params()):
+            np.testing.assert_allclose(Wg, want[f"{2 * j}.W"], rtol=2e-4, atol=2e-6)
+            np.testing.assert_allclose(bg, want[f"{2 * j}.b"], rtol=2e-4, atol=2e-6)
+            # the trained layers moved by many tolerances
+            assert j == 0 or (np.abs(want[f"{2 * j}.W"] - W[j]) / (2e-6 + 2e-4 * np.abs(W[j]))).max() >= 10
+        e, f, c = obj.stats()
+        assert f == rst.frames == 5 * B
+        np.testing.assert_allclose(e, rst.xent, rtol=1e-5)
 
 
 def test_generic_component_path_matches_fused():
